@@ -28,10 +28,17 @@ Other BASELINE configs (``--workload``):
       ray-samples/s (fwd+bwd+update); also the val PSNR before / after the adaptation.
   c5a placement variant: rank r adapts expert r alone (active_module), no collective.
 
-Also reported: roofline of the fused render kernel (HIP events bracketing exactly that launch on
-its stream), and on rank 0 at N=1 a CPU baseline: the C oracle (oracle/, a fixture-pinned port of
-the reference CPU path) rendering the same batch on the host cores, whose output also gives the
-PSNR of the GPU render against the CPU path.
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) sets up, warms up, times the N steps and
+prints one JSON line with the headline figure (``value``, ``ms_per_step``).  ``--dump-outputs DIR``
+also writes what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB
+in all; a fixed seeded sample of a larger array), so two builds can be compared output for output:
+the inputs are seeded and identical from run to run.
+
+``--full`` adds everything else to the line: the roofline of the dominant kernel (HIP events
+bracketing exactly that launch on its stream, for the training workloads timed by eager steps after
+the timed ones), the validation PSNR of the adaptation workload, and on rank 0 a CPU baseline: the
+C oracle (oracle/, a fixture-pinned port of the reference CPU path) rendering the same batch on the
+host cores, whose output also gives the PSNR of the GPU render against the CPU path.
 """
 from __future__ import annotations
 
@@ -384,6 +391,74 @@ def load_gather_ceiling():
         return None
 
 
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def named_outputs(out, names=None, prefix="out"):
+    """Flatten what a step returned (a tensor, a number, or nested tuples / lists / dicts of them; None
+    entries dropped) into [(name, value)]: ``names`` for the top-level entries where given, else their
+    position (out0, out1_2, ...)."""
+    if out is None:
+        return []
+    if isinstance(out, dict):
+        items = [(f"{prefix}_{k}", v) for k, v in out.items()]
+    elif isinstance(out, (tuple, list)):
+        items = [(names[i] if names and i < len(names) else f"{prefix}{i}", v) for i, v in enumerate(out)]
+    else:
+        return [(names[0] if names else prefix, out)]
+    flat = []
+    for n, v in items:
+        flat += named_outputs(v, None, n + "_") if isinstance(v, (tuple, list, dict)) else [(n, v)]
+    return [(n, v) for n, v in flat if v is not None]
+
+
+def dump_outputs(out, directory, names=None):
+    """--dump-outputs: every array of the last timed step as directory/<name>.npy, float32 (float64 for
+    float64 and integer values).  The total stays under DUMP_BYTES_MAX: each array larger than an even share
+    of it is cut to a fixed sample of its flattened elements (sorted indices from numpy's default_rng(0)), so
+    the same elements are kept from run to run and from build to build.  Returns {name: description}."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = []
+    for n, v in named_outputs(out, names):
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            v = v.to(torch.float64 if v.dtype == torch.float64 or not (v.is_floating_point() or v.dtype == torch.bool)
+                     else torch.float32).cpu().numpy()
+        else:
+            v = np.asarray(v)
+            if v.dtype.kind not in "fiub":      # not an array or a number (a name, a plan object): nothing to compare
+                continue
+            v = v.astype(np.float32 if v.dtype.kind == "f" and v.dtype.itemsize <= 4 or v.dtype.kind == "b"
+                         else np.float64)
+        arrays.append((n, v))
+    written = {}
+    share = DUMP_BYTES_MAX // max(len(arrays), 1)
+    over = sum(v.nbytes for _, v in arrays) > DUMP_BYTES_MAX
+    for n, v in arrays:
+        what = {"shape": list(v.shape), "dtype": str(v.dtype)}
+        if over and v.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, v.size, share // v.itemsize))
+            v = v.reshape(-1)[idx]
+            what["sampled_elements"] = int(idx.size)
+        np.save(d / f"{n}.npy", v)
+        written[n] = what
+    return written
+
+
+def teardown(world: int, rank: int) -> None:
+    """N > 1: release every graph that captured an RCCL collective (--ep-graph), then destroy the group,
+    bounded: RCCL's teardown waits for such graphs."""
+    if world <= 1:
+        return
+    from adaptive_city_nerf_amd.expert_parallel import shutdown
+    if not shutdown(timeout=120.0):
+        print(f"bench.py rank {rank}: destroy_process_group did not return within 120 s", file=sys.stderr,
+              flush=True)
+        sys.stdout.flush()
+        os._exit(0)
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -417,6 +492,13 @@ def main():
                     help="timed steps (default 200 for the sub-millisecond c2 / c3 steps, whose fixed start-up "
                          "latency would otherwise weigh on a 20-step window; 20 for the others)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report what the headline figure does not need: the dominant kernel's "
+                         "roofline, the CPU baseline and the PSNR against the CPU path (--cpu-seconds, --cpu-rays, "
+                         "--no-cpu-baseline), the adaptation workload's validation PSNR")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a fixed seeded sample of a larger array; rank 0's outputs)")
     ap.add_argument("--workload", choices=["c2", "c3", "c4", "c5", "c5a", "occ", "meta", "data", "clusters"], default="c2")
     ap.add_argument("--rays", type=int, default=4096, help="rays per GPU (c2, c3)")
     ap.add_argument("--samples", type=int, default=256)
@@ -424,15 +506,15 @@ def main():
     ap.add_argument("--layout", choices=["replicated", "expert"], default="replicated",
                     help="c4: experts replicated + rays sharded by owning expert (all-gather of rendered rays), or "
                          "one expert per GPU (all-to-all of per-sample records, expert_parallel.py)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: least duration of the CPU baseline")
     ap.add_argument("--opaque", type=float, default=0.0,
                     help="c2: add this to every expert's sigma_head bias (density x e^B): a synthetic opaque "
                          "scene on which early ray termination has rays to stop")
     ap.add_argument("--tau", type=float, default=0.0,
                     help="c2: early ray termination threshold on transmittance (wavefront scan; 0 = off, the "
-                         "reference's behaviour); the line then reports the RGB error against tau = 0")
+                         "reference's behaviour); with --full the line then reports the RGB error against tau = 0")
     ap.add_argument("--cpu-rays", type=int, default=4096, help="rays in the CPU-baseline / PSNR sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline")
     ap.add_argument("--inner-iter", type=int, default=8, help="meta: inner steps (configs/train.json)")
     ap.add_argument("--support-rays", type=int, default=4000, help="meta: support rays per task")
     ap.add_argument("--query-rays", type=int, default=2000, help="meta: query rays per task")
@@ -707,7 +789,7 @@ def main():
             model.train()
             p_, g_ = color_space_transformer(pr, gt_val, color_space="linear")
             return float(-10.0 * torch.log10(torch.mean((p_.double() - g_.double()) ** 2).clamp_min(1e-8)))
-        psnr_before = val_psnr()
+        psnr_before = val_psnr() if a.full else None
         model.train()
         opt = aoptim.build_optimizer(P, model)
         samples_per_step = (1 if strong else world) * bsz * S
@@ -852,6 +934,35 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(out, a.dump_outputs, ("rgb", "depth", "weights", "acc") if a.workload == "c2" else None)
+    if not a.full:
+        # a plain run: the headline figure alone (the same timed region as --full; nothing else is measured)
+        ops.EVENT_HOOK = None
+        if world > 1:
+            t = torch.tensor([dt], device=device, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t[0])
+        if rank == 0:
+            amp = a.workload in ("c5", "meta") and a.mlp_precision == "amp"
+            line = {
+                "metric": "ray-samples/sec + PSNR, 4096 rays×256 samples, 1/2/4/8 MI355X",
+                "value": round(samples_per_step * a.steps / dt, 1),
+                "unit": "rays/s" if a.workload == "data" else "ray-samples/s", "n_gpus": world, "steps": a.steps,
+                "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True,
+                "scaling": "strong" if (a.workload == "c4" or (a.workload == "c5" and a.c5_scaling == "strong"))
+                           else "weak", "vs_baseline": None,
+                "dtype": "f16 MLP products / f32 accumulate (use_amp), f32 elsewhere" if amp else "f32",
+                "data": "synthetic (formula-filled hash table, seeded MLP init; rays from the reference's "
+                        "validation camera geometry)",
+                "config": {"workload": a.workload, "samples_per_ray": S, "parallelism": f"ray-sharded x{world}"},
+                "full": False}
+            if dumped is not None:
+                line["dumped_outputs"] = dumped
+            print(json.dumps(line), flush=True)
+        teardown(world, rank)
+        return
     if a.workload == "c5a" and graphed is not None:
         # graph replays run no Python, so the Adam launch is timed by one eager step afterwards
         from adaptive_city_nerf_amd import optim as aoptim
@@ -1251,7 +1362,10 @@ def main():
             "cpu_baseline": cpu,
             "psnr_vs_cpu_path_db": None if psnr is None else round(psnr, 2),
             "rgb_max_abs_err_vs_cpu_path": maxerr,
+            "full": True,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if a.workload == "c2" and a.tau > 0:
             with torch.no_grad():
                 ref0, _, _, acc0 = render_rays(model, rays, ray_samples=S, bg_color_default="white")
@@ -1326,15 +1440,7 @@ def main():
                 if a.workload == "meta" and meta_scaler is not None:
                     line["amp_scaler"] = meta_scaler.state_dict()
         print(json.dumps(line))
-    if world > 1:
-        # release every graph that captured an RCCL collective (--ep-graph), then destroy the group, bounded:
-        # RCCL's teardown waits for such graphs
-        from adaptive_city_nerf_amd.expert_parallel import shutdown
-        if not shutdown(timeout=120.0):
-            print(f"bench.py rank {rank}: destroy_process_group did not return within 120 s", file=sys.stderr,
-                  flush=True)
-            sys.stdout.flush()
-            os._exit(0)
+    teardown(world, rank)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 : > $OUT
 for v in "$@"; do
   lib=adaptive_city_nerf_amd/libacnerf.so; [ "$v" = base ] || lib=build_variants/libacnerf_$v.so
-  ACNERF_LIB=$lib timeout -k 10 120 python bench.py --steps 50 --warmup 5 --cpu-seconds 0.3 $BENCH_ARGS \
+  ACNERF_LIB=$lib timeout -k 10 120 python bench.py --full --steps 50 --warmup 5 --cpu-seconds 0.3 $BENCH_ARGS \
       > gpurun_out/ab_$v.json 2> gpurun_out/ab_$v.err || { echo "variant $v failed"; exit 1; }
   python - "$v" >> $OUT <<'PY'
 import json, sys

@@ -3,6 +3,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+OUT=${ACN_OUT:-bench_out}; mkdir -p "$OUT"   # where the --full bench lines go
 SEL=${1:-tests}
 TAG=${2:-q}
 shift 2
@@ -11,6 +12,6 @@ rc=$?
 echo "pytest rc=$rc"
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 for w in "$@"; do
-  timeout -k 10 300 python -u bench.py $w > gpurun_out/bench_${TAG}_$(echo $w | tr -d ' -' ).json 2> gpurun_out/bench_${TAG}_$(echo $w | tr -d ' -').err || { echo "bench $w failed"; exit 3; }
+  timeout -k 10 300 python -u bench.py --full $w > $OUT/bench_${TAG}_$(echo $w | tr -d ' -' ).json 2> $OUT/bench_${TAG}_$(echo $w | tr -d ' -').err || { echo "bench $w failed"; exit 3; }
 done
 echo "gpu_quick done"
