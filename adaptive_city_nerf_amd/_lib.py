@@ -82,6 +82,8 @@ SIGNATURES = {
     "acn_hashgrid_fwd": ([vp, i64, vp, vp, i32, i32, i32, i32, vp, vp], C.c_int),
     "acn_hashgrid_bwd": ([vp, i64, vp, vp, i32, i32, i32, i32, vp, vp], C.c_int),
     "acn_sh_fwd": ([vp, i64, i32, vp, vp], C.c_int),
+    "acn_hashgrid_bwd_input": ([vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp], C.c_int),
+    "acn_sh_bwd": ([vp, i64, i32, vp, vp, vp], C.c_int),
     "acn_workspace_bytes": ([i32], sz),
     "acn_pack_experts": ([vp, vp, i32, vp, sz, vp], C.c_int),
     "acn_field_fwd": ([vp, i64, i64, vp, vp, i32, vp, sz, vp, vp], C.c_int),

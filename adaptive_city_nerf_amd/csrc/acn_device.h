@@ -145,6 +145,57 @@ __device__ __forceinline__ void sh_encode(float dx, float dy, float dz, float* c
     sh_components<DEGREE>(dx / n, dy / n, dz / n, c, kz);
 }
 
+// Gradient of sum_c g[c] * Y_c(x, y, z) in the unit vector (x, y, z): the polynomials of sh_components
+// differentiated term by term (Y_0 is constant).  Plain mul/add, accumulated in component order.
+template <int DEGREE>
+__device__ __forceinline__ void sh_components_bwd(float x, float y, float z, const float* g, float& gx, float& gy,
+                                                  float& gz) {
+    const float xx = x * x, yy = y * y, zz = z * z;
+    gx = 0.0f; gy = 0.0f; gz = 0.0f;
+    if (DEGREE > 0) {
+        gy += 0.4886025119029199f * g[1];
+        gz += 0.4886025119029199f * g[2];
+        gx += 0.4886025119029199f * g[3];
+    }
+    if (DEGREE > 1) {
+        const float k4 = 1.0925484305920792f, k6 = 0.9461746957575601f, k8 = 0.5462742152960396f;
+        gx += (k4 * y) * g[4];  gy += (k4 * x) * g[4];
+        gy += (k4 * z) * g[5];  gz += (k4 * y) * g[5];
+        gz += ((2.0f * k6) * z) * g[6];
+        gx += (k4 * z) * g[7];  gz += (k4 * x) * g[7];
+        gx += ((2.0f * k8) * x) * g[8];  gy -= ((2.0f * k8) * y) * g[8];
+    }
+    if (DEGREE > 2) {
+        const float k9 = 0.5900435899266435f, k10 = 2.890611442640554f, k11 = 0.4570457994644658f;
+        const float k12 = 0.3731763325901154f, k14 = 1.445305721320277f;
+        const float d3 = 3.0f * (xx - yy), z51 = 5.0f * zz - 1.0f;
+        gx += ((6.0f * k9) * (x * y)) * g[9];   gy += (k9 * d3) * g[9];
+        gx += (k10 * (y * z)) * g[10];  gy += (k10 * (x * z)) * g[10];  gz += (k10 * (x * y)) * g[10];
+        gy += (k11 * z51) * g[11];  gz += ((10.0f * k11) * (y * z)) * g[11];
+        gz += (k12 * (15.0f * zz - 3.0f)) * g[12];
+        gx += (k11 * z51) * g[13];  gz += ((10.0f * k11) * (x * z)) * g[13];
+        gx += ((2.0f * k14) * (x * z)) * g[14];  gy -= ((2.0f * k14) * (y * z)) * g[14];  gz += (k14 * (xx - yy)) * g[14];
+        gx += (k9 * d3) * g[15];  gy -= ((6.0f * k9) * (x * y)) * g[15];
+    }
+    if (DEGREE > 3) {
+        const float k16 = 2.5033429417967046f, k17 = 1.7701307697799304f, k18 = 0.9461746957575601f;
+        const float k19 = 0.6690465435572892f, k20 = 0.10578554691520431f, k22 = 0.47308734787878004f;
+        const float k24 = 0.6258357354491761f;
+        const float a = 3.0f * xx - yy, b = xx - 3.0f * yy, d3 = 3.0f * (xx - yy);
+        const float z71 = 7.0f * zz - 1.0f, z73 = 7.0f * zz - 3.0f, z213 = 21.0f * zz - 3.0f;
+        gx += (k16 * (y * a)) * g[16];  gy += (k16 * (x * b)) * g[16];
+        gx += ((6.0f * k17) * ((x * y) * z)) * g[17];  gy += (k17 * (z * d3)) * g[17];  gz += (k17 * (y * a)) * g[17];
+        gx += (k18 * (y * z71)) * g[18];  gy += (k18 * (x * z71)) * g[18];  gz += ((14.0f * k18) * ((x * y) * z)) * g[18];
+        gy += (k19 * (z * z73)) * g[19];  gz += (k19 * (y * z213)) * g[19];
+        gz += (k20 * (z * (140.0f * zz - 60.0f))) * g[20];
+        gx += (k19 * (z * z73)) * g[21];  gz += (k19 * (x * z213)) * g[21];
+        gx += ((2.0f * k22) * (x * z71)) * g[22];  gy -= ((2.0f * k22) * (y * z71)) * g[22];
+        gz += ((14.0f * k22) * ((xx - yy) * z)) * g[22];
+        gx += (k17 * (z * d3)) * g[23];  gy -= ((6.0f * k17) * ((x * y) * z)) * g[23];  gz += (k17 * (x * b)) * g[23];
+        gx += ((4.0f * k24) * (x * b)) * g[24];  gy -= ((4.0f * k24) * (y * a)) * g[24];
+    }
+}
+
 // One level of HashGridEncoder._torch_forward split in two halves so that callers can keep the
 // gathers of several levels in flight: hash_issue computes the 8 corner rows and issues their
 // loads, hash_finish interpolates once they have landed.  Same arithmetic as hash_level_f2.
@@ -383,6 +434,21 @@ __device__ __forceinline__ void hash_issue_b(__amdgpu_buffer_rsrc_t rs, uint32_t
     p.wx = wx;
     p.wy = wy;
     p.wz = wz;
+}
+
+// The 8 corner rows of a landed hash_issue_x, in hash_issue's order (f index: bit0 = x1, bit1 = z1, bit2 = y1), for
+// callers that need the rows themselves (the input-gradient kernel, encoders.hip).  The weights are not copied.
+__device__ __forceinline__ void hash_rows_x(const HashPendingX& p, float2 (&f)[8]) {
+    const bool xodd = (p.sel & 16u) != 0u;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const bool hi = ((p.sel >> c) & 1u) != 0u;
+        const u32x4_t q = p.q[c];
+        const uint32_t l0 = hi ? q[2] : q[0], l1 = hi ? q[3] : q[1];
+        const uint32_t e0 = hi ? q[0] : q[2], e1 = hi ? q[1] : q[3];
+        f[2 * c] = make_float2(__uint_as_float(l0), __uint_as_float(l1));
+        f[2 * c + 1] = make_float2(__uint_as_float(xodd ? p.r[c][0] : e0), __uint_as_float(xodd ? p.r[c][1] : e1));
+    }
 }
 
 template <int INTERP>

@@ -1,7 +1,8 @@
-// encoders.hip -- standalone HashGridEncoder forward/backward and SHEncoder forward (gfx950).
+// encoders.hip -- standalone HashGridEncoder and SHEncoder forward/backward (gfx950).
 //
 // Replaces models/encodings.py:331-381 (HashGridEncoder._torch_forward, _hash :308-316, _gather
-// :318-329) and :133-151 (SHEncoder.forward).  One lane per (point, level): the L lanes of a
+// :318-329) and :133-151 (SHEncoder.forward), and their autograd in the table, the points and the
+// directions.  One lane per (point, level): the L lanes of a
 // point are adjacent, so the (M, L*F) output row of a point is written as one contiguous
 // L*F*4-byte segment (128 B for the reference's L=16, F=2) and the point's x01 is a broadcast.
 #include "acn_device.h"
@@ -509,6 +510,180 @@ MergeCfg merge_cfg(int L, int log2T, int levels = ACN_HASH_BWD_MERGE) {
     return c;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Input gradient: grad_x (M,3) of sum(out * grad_out), the autograd of encodings.py:331-381 in x.  Per level the
+// forward is out_f = interp(rows_f; w(x * res)), so
+//   grad_x[a] = sum_l res_l * dw_a * sum_f grad_out[l,f] * d/dw_a interp(rows_f; w)
+// with dw = 1 (Linear) or 6 w (1 - w) (Smoothstep, the lerps on the smoothed w).  interp is linear in the rows, so
+// the features are folded first (v_corner = sum_f g_f * row_f) and one scalar trilinear form is differentiated:
+// d/dw_z is the difference of the two z-planes, d/dw_y the z-lerp of the y-differences of the x-lerps, d/dw_x the
+// y -> z lerp of the four x-differences.  Nearest has a zero gradient (acn_hashgrid_bwd_input writes zeros).
+//
+// Gather forms: F == 2 with a table of at most 2 GiB reads the rows through a buffer resource over the whole table
+// with 32-bit offsets (hash_issue_x, exactly the forward's gathers; hashgrid_bwd_input_f2).  Larger tables and
+// F != 2 use the 64-bit pointer form, as hashgrid_fwd_f2 / hashgrid_fwd_gen do (hashgrid_bwd_input_gen).
+//
+// No atomics: a point's level terms are summed in a fixed order that depends on nothing but L -- an xor-shuffle
+// tree over the point's L adjacent lanes when L is a power of two (TREE: one lane per (point, level), as the
+// forward), else one lane per point adding levels 0 .. L-1 in turn.
+struct LevelGrad {
+    float x, y, z;
+};
+
+// v[]: the folded corner values in hash_issue's order (bit0 = x1, bit1 = z1, bit2 = y1); w: the raw weights
+template <int INTERP>
+__device__ __forceinline__ LevelGrad level_grad(const float (&v)[8], float wx, float wy, float wz, float r) {
+    float dx = r, dy = r, dz = r;
+    if (INTERP == 2) {
+        dx = r * ((6.0f * wx) * (1.0f - wx));
+        dy = r * ((6.0f * wy) * (1.0f - wy));
+        dz = r * ((6.0f * wz) * (1.0f - wz));
+        wx = (wx * wx) * (3.0f - 2.0f * wx);
+        wy = (wy * wy) * (3.0f - 2.0f * wy);
+        wz = (wz * wz) * (3.0f - 2.0f * wz);
+    }
+    const float ax = 1.0f - wx, ay = 1.0f - wy, az = 1.0f - wz;
+    const float c00 = v[0] * ax + v[1] * wx, c01 = v[2] * ax + v[3] * wx;   // c{y}{z}: the forward's x-lerps
+    const float c10 = v[4] * ax + v[5] * wx, c11 = v[6] * ax + v[7] * wx;
+    const float c0 = c00 * ay + c10 * wy, c1 = c01 * ay + c11 * wy;
+    const float d00 = v[1] - v[0], d01 = v[3] - v[2], d10 = v[5] - v[4], d11 = v[7] - v[6];
+    const float gx = (d00 * ay + d10 * wy) * az + (d01 * ay + d11 * wy) * wz;
+    const float gy = (c10 - c00) * az + (c11 - c01) * wz;
+    const float gz = c1 - c0;
+    return LevelGrad{dx * gx, dy * gy, dz * gz};
+}
+
+template <int INTERP>
+__device__ __forceinline__ LevelGrad level_grad_f2(__amdgpu_buffer_rsrc_t rs, int l, int log2T, uint32_t mask,
+                                                   float r, float px, float py, float pz, float2 g) {
+    const float sx = px * r, sy = py * r, sz = pz * r;
+    acn::HashPendingX p;
+    acn::hash_issue_x<INTERP>(rs, (uint32_t)l << (log2T + 3), sx, sy, sz, mask, p);
+    float2 f[8];
+    acn::hash_rows_x(p, f);
+    float v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = g.x * f[c].x + g.y * f[c].y;
+    return level_grad<INTERP>(v, sx - floorf(sx), sy - floorf(sy), sz - floorf(sz), r);
+}
+
+template <int INTERP, bool TREE>
+__global__ void __launch_bounds__(256) hashgrid_bwd_input_f2(const float* __restrict__ x01, int64_t M,
+                                                             const float2* __restrict__ gout,
+                                                             const float2* __restrict__ table, Res32 res, int L,
+                                                             int log2T, float* __restrict__ gx) {
+    const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)table, (short)0, (int)((uint32_t)L << (log2T + 3)), 0x00020000);
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (TREE) {
+        // L is a power of two <= 32: a point's lanes are one aligned group of a wave, live or idle together
+        const int64_t m = gid / L;
+        const int l = (int)(gid - m * L);
+        LevelGrad a{0.0f, 0.0f, 0.0f};
+        if (m < M)
+            a = level_grad_f2<INTERP>(rs, l, log2T, mask, (float)res.v[l], x01[3 * m], x01[3 * m + 1], x01[3 * m + 2],
+                                      gout[m * L + l]);
+        for (int off = 1; off < L; off <<= 1) {
+            a.x += __shfl_xor(a.x, off);
+            a.y += __shfl_xor(a.y, off);
+            a.z += __shfl_xor(a.z, off);
+        }
+        if (m < M && l == 0) {
+            gx[3 * m] = a.x;
+            gx[3 * m + 1] = a.y;
+            gx[3 * m + 2] = a.z;
+        }
+    } else {
+        const int64_t m = gid;
+        if (m >= M) return;
+        const float px = x01[3 * m], py = x01[3 * m + 1], pz = x01[3 * m + 2];
+        LevelGrad a{0.0f, 0.0f, 0.0f};
+        for (int l = 0; l < L; ++l) {
+            const LevelGrad t = level_grad_f2<INTERP>(rs, l, log2T, mask, (float)res.v[l], px, py, pz, gout[m * L + l]);
+            a.x += t.x;
+            a.y += t.y;
+            a.z += t.z;
+        }
+        gx[3 * m] = a.x;
+        gx[3 * m + 1] = a.y;
+        gx[3 * m + 2] = a.z;
+    }
+}
+
+// any F, any table size: 64-bit row addresses, one lane per point
+template <int INTERP>
+__global__ void __launch_bounds__(256) hashgrid_bwd_input_gen(const float* __restrict__ x01, int64_t M,
+                                                              const float* __restrict__ gout,
+                                                              const float* __restrict__ table, Res32 res, int L,
+                                                              int log2T, int F, float* __restrict__ gx) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
+    const float px = x01[3 * m], py = x01[3 * m + 1], pz = x01[3 * m + 2];
+    LevelGrad a{0.0f, 0.0f, 0.0f};
+    for (int l = 0; l < L; ++l) {
+        const float r = (float)res.v[l];
+        const float sx = px * r, sy = py * r, sz = pz * r;
+        const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
+        const uint32_t x0 = (uint32_t)(int)fx, x1 = x0 + 1u;
+        const uint32_t y0 = (uint32_t)(int)fy * acn::kP1, y1 = y0 + acn::kP1;
+        const uint32_t z0 = (uint32_t)(int)fz * acn::kP2, z1 = z0 + acn::kP2;
+        const uint32_t rows[8] = {x0 ^ y0 ^ z0, x1 ^ y0 ^ z0, x0 ^ y0 ^ z1, x1 ^ y0 ^ z1,
+                                  x0 ^ y1 ^ z0, x1 ^ y1 ^ z0, x0 ^ y1 ^ z1, x1 ^ y1 ^ z1};
+        const float* tl = table + ((int64_t)l << log2T) * F;
+        const float* g = gout + (m * L + l) * F;
+        float v[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float* e = tl + (int64_t)(rows[c] & mask) * F;
+            float s = 0.0f;
+            for (int f = 0; f < F; ++f) s += g[f] * e[f];
+            v[c] = s;
+        }
+        const LevelGrad t = level_grad<INTERP>(v, sx - fx, sy - fy, sz - fz, r);
+        a.x += t.x;
+        a.y += t.y;
+        a.z += t.z;
+    }
+    gx[3 * m] = a.x;
+    gx[3 * m + 1] = a.y;
+    gx[3 * m + 2] = a.z;
+}
+
+__global__ void __launch_bounds__(256) zero_f32(float* __restrict__ p, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = 0.0f;
+}
+
+// Backward of sh_encode (acn_device.h) in the unnormalised direction: g_n through the polynomials, then through
+// n = d / max(|d|, 1e-9) as torch differentiates norm and clamp_min (the clamp passes no gradient below 1e-9).
+template <int DEGREE>
+__global__ void __launch_bounds__(256) sh_bwd_kernel(const float* __restrict__ d, int64_t M,
+                                                     const float* __restrict__ gout, float* __restrict__ gd) {
+    constexpr int C = (DEGREE + 1) * (DEGREE + 1);
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    const float dx = d[3 * m], dy = d[3 * m + 1], dz = d[3 * m + 2];
+    const float nrm = acn::norm3(dx, dy, dz);
+    const float n = acn::clamp_min_nan(nrm, 1e-9f);
+    const float x = dx / n, y = dy / n, z = dz / n;
+    float g[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) g[i] = gout[m * C + i];
+    float gx, gy, gz;
+    acn::sh_components_bwd<DEGREE>(x, y, z, g, gx, gy, gz);
+    if (nrm >= 1e-9f) {
+        const float dot = (x * gx + y * gy) + z * gz;
+        gx = gx - x * dot;
+        gy = gy - y * dot;
+        gz = gz - z * dot;
+    }
+    gd[3 * m] = gx / n;
+    gd[3 * m + 1] = gy / n;
+    gd[3 * m + 2] = gz / n;
+}
+
 template <int DEGREE>
 __global__ void __launch_bounds__(256) sh_fwd_kernel(const float* __restrict__ d, int64_t M,
                                                      float* __restrict__ out) {
@@ -616,6 +791,58 @@ extern "C" int acn_sh_fwd(const float* d, int64_t M, int levels, float* out, voi
         default: hipLaunchKernelGGL(sh_fwd_kernel<4>, grid, block, 0, s, d, M, out); break;
     }
     return acn_check_launch("acn_sh_fwd");
+}
+
+extern "C" int acn_hashgrid_bwd_input(const float* x01, int64_t M, const float* grad_out, const float* table,
+                                      const int32_t* res, int L, int log2T, int F, int interp, float* grad_x,
+                                      void* stream) {
+    ACN_REQUIRE(M >= 0, "acn_hashgrid_bwd_input: M must be >= 0");
+    ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS, "acn_hashgrid_bwd_input: levels must be in [1, %d], got %d", ACN_MAX_LEVELS, L);
+    ACN_REQUIRE(log2T >= 1 && log2T <= 30, "acn_hashgrid_bwd_input: log2_hashmap_size must be in [1, 30], got %d", log2T);
+    ACN_REQUIRE(F >= 1, "acn_hashgrid_bwd_input: features_per_level must be >= 1, got %d", F);
+    ACN_REQUIRE(interp >= 0 && interp <= 2, "acn_hashgrid_bwd_input: bad interpolation %d", interp);
+    ACN_REQUIRE(res != nullptr, "acn_hashgrid_bwd_input: res is NULL");
+    if (M == 0) return ACN_OK;
+    ACN_REQUIRE(x01 && grad_out && table && grad_x, "acn_hashgrid_bwd_input: NULL pointer");
+    Res32 r{};
+    for (int i = 0; i < L; ++i) r.v[i] = res[i];
+    const dim3 block(256);
+    hipStream_t s = (hipStream_t)stream;
+    auto blocks = [](int64_t threads) { return dim3((unsigned)((threads + 255) / 256)); };
+    if (interp == 0) {  // rint() is piecewise constant: the gradient is exactly 0
+        hipLaunchKernelGGL(zero_f32, blocks(3 * M), block, 0, s, grad_x, 3 * M);
+    } else if (F == 2 && ((uint64_t)L << (log2T + 3)) <= (1ull << 31)) {
+        const float2* g = (const float2*)grad_out;
+        const float2* t = (const float2*)table;
+        if ((L & (L - 1)) == 0) {
+            if (interp == 1) hipLaunchKernelGGL((hashgrid_bwd_input_f2<1, true>), blocks(M * L), block, 0, s, x01, M, g, t, r, L, log2T, grad_x);
+            else hipLaunchKernelGGL((hashgrid_bwd_input_f2<2, true>), blocks(M * L), block, 0, s, x01, M, g, t, r, L, log2T, grad_x);
+        } else {
+            if (interp == 1) hipLaunchKernelGGL((hashgrid_bwd_input_f2<1, false>), blocks(M), block, 0, s, x01, M, g, t, r, L, log2T, grad_x);
+            else hipLaunchKernelGGL((hashgrid_bwd_input_f2<2, false>), blocks(M), block, 0, s, x01, M, g, t, r, L, log2T, grad_x);
+        }
+    } else {
+        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_input_gen<1>, blocks(M), block, 0, s, x01, M, grad_out, table, r, L, log2T, F, grad_x);
+        else hipLaunchKernelGGL(hashgrid_bwd_input_gen<2>, blocks(M), block, 0, s, x01, M, grad_out, table, r, L, log2T, F, grad_x);
+    }
+    return acn_check_launch("acn_hashgrid_bwd_input");
+}
+
+extern "C" int acn_sh_bwd(const float* d, int64_t M, int levels, const float* g_out, float* g_d, void* stream) {
+    ACN_REQUIRE(levels >= 1 && levels <= 5, "acn_sh_bwd: Supported levels in [1, 5], got %d", levels);
+    ACN_REQUIRE(M >= 0, "acn_sh_bwd: M must be >= 0");
+    if (M == 0) return ACN_OK;
+    ACN_REQUIRE(d && g_out && g_d, "acn_sh_bwd: NULL pointer");
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    switch (levels) {
+        case 1: hipLaunchKernelGGL(sh_bwd_kernel<0>, grid, block, 0, s, d, M, g_out, g_d); break;
+        case 2: hipLaunchKernelGGL(sh_bwd_kernel<1>, grid, block, 0, s, d, M, g_out, g_d); break;
+        case 3: hipLaunchKernelGGL(sh_bwd_kernel<2>, grid, block, 0, s, d, M, g_out, g_d); break;
+        case 4: hipLaunchKernelGGL(sh_bwd_kernel<3>, grid, block, 0, s, d, M, g_out, g_d); break;
+        default: hipLaunchKernelGGL(sh_bwd_kernel<4>, grid, block, 0, s, d, M, g_out, g_d); break;
+    }
+    return acn_check_launch("acn_sh_bwd");
 }
 
 extern "C" int acn_hashgrid_fwd_pairs(const float* x01, const int32_t* pk, const int64_t* seg, int K,

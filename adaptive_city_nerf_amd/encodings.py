@@ -15,6 +15,7 @@ from typing import Literal, Optional
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import ops
 from ._lib import INTERP, AcnError
@@ -68,6 +69,42 @@ def components_from_spherical_harmonics(degree: int, directions: torch.Tensor) -
     return c
 
 
+def wants_grad(*ts) -> bool:
+    """True when autograd is recording and one of the tensors requires grad.  Every fused or no-grad shortcut of
+    the package asks this about its inputs (points, directions, rays) as well as its weights, and takes a
+    differentiable path when it holds."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+def _first_order_only(what: str) -> None:
+    """The input-gradient kernels are not differentiable themselves: refuse a backward that records a graph
+    (create_graph=True) or runs in a second-order scope, instead of handing back a gradient that autograd would
+    treat as constant."""
+    from .ray_rendering import _second_order
+    if torch.is_grad_enabled() or _second_order():
+        raise AcnError(f"{what}: second-order gradients through the input gradient are not implemented on the HIP "
+                       "path (create_graph=True / ray_rendering.second_order())")
+
+
+class _SHFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d, levels):
+        ctx.save_for_backward(d)
+        ctx.levels = levels
+        return ops.sh_fwd(d, levels).to(d.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("SHEncoder")
+        return _SHFn._backward(ctx, g)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        return ops.sh_bwd(d, g, ctx.levels).to(d.dtype), None
+
+
 class SHEncoder(nn.Module):
     """Real spherical harmonics of degree levels-1 (encodings.py:84-151) on the HIP kernel."""
 
@@ -86,8 +123,8 @@ class SHEncoder(nn.Module):
 
     def forward(self, d: torch.Tensor) -> torch.Tensor:
         assert d.shape[-1] == 3, f"Expected (...,3); got {tuple(d.shape)}"
-        if d.requires_grad:
-            raise AcnError("SHEncoder: gradients w.r.t. directions are not implemented on the HIP path")
+        if wants_grad(d):
+            return _SHFn.apply(d, self.levels)
         return ops.sh_fwd(d, self.levels).to(d.dtype)
 
 
@@ -112,7 +149,12 @@ def accumulate_table_grad():
 class _HashGridFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x01, table, enc):
-        ctx.save_for_backward(x01)
+        if ctx.needs_input_grad[0]:
+            # the point gradient reads the table in backward: saved, so that autograd catches an in-place change
+            # of it between forward and backward
+            ctx.save_for_backward(x01, table)
+        else:
+            ctx.save_for_backward(x01)
         ctx.enc = enc
         ctx.table = table
         return ops.hashgrid_fwd(x01, table, enc._res_host, enc.log2_hashmap_size, enc.features_per_level,
@@ -120,11 +162,24 @@ class _HashGridFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        (x01,) = ctx.saved_tensors
-        enc = ctx.enc
         if ctx.needs_input_grad[0]:
-            raise AcnError("HashGridEncoder: gradients w.r.t. the input points are not implemented on the HIP "
-                           "path (the reference pipelines never request them)")
+            _first_order_only("HashGridEncoder")
+            return _HashGridFn._backward_points(ctx, g)
+        return _HashGridFn._backward_table(ctx, g)
+
+    @staticmethod
+    @once_differentiable
+    def _backward_points(ctx, g):
+        x01, table = ctx.saved_tensors
+        enc = ctx.enc
+        gx = ops.hashgrid_bwd_input(x01, g, table, enc._res_host, enc.log2_hashmap_size, enc.features_per_level,
+                                    enc._interp_code).to(x01.dtype)
+        return gx, _HashGridFn._backward_table(ctx, g)[1], None
+
+    @staticmethod
+    def _backward_table(ctx, g):
+        x01 = ctx.saved_tensors[0]
+        enc = ctx.enc
         gt = None
         if ctx.needs_input_grad[1]:
             tab = ctx.table

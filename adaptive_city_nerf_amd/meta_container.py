@@ -17,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .encodings import FrequencyEncoder, SHEncoder
+from .encodings import FrequencyEncoder, SHEncoder, wants_grad
 from .meta_ngp import MetaNGP
 from .metamodule import MetaModule
 
@@ -133,7 +133,20 @@ class MetaContainer(MetaModule):
         assert pts.dim() == 2 and pts.shape[-1] == 3, "pts must be (N,3)"
         assert self.centroids.shape[0] > 0, "No centroids provided."
         with torch.no_grad():
-            return ops.routing_fwd(pts.to(self.centroids.device), self.routing_spec())
+            weights, hard = ops.routing_fwd(pts.to(self.centroids.device), self.routing_spec())
+        if weights is not None and wants_grad(pts):
+            weights = self._soft_weights(pts.to(self.centroids.device), weights > 0)
+        return weights, hard
+
+    def _soft_weights(self, pts: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+        """The soft weights w_k = (1/d_k) [k in mask] / sum as torch ops, differentiable in the points; the mask
+        (the experts within boundary_margin of the nearest) is the routing kernel's.  Distances in the kernel's
+        mm form, x^2 + c^2 - 2 x.c clamped at 0 (the clamp at 1e-12 under the root is its max(d, 1e-6))."""
+        cols = list(self._coord_idx)
+        x, c = pts[:, cols].float(), self.centroids[:, cols].float()
+        s = (x * x).sum(-1, keepdim=True) + (c * c).sum(-1)[None, :] - 2.0 * (x @ c.t())
+        inv = torch.where(mask, 1.0 / s.clamp_min(1e-12).sqrt(), torch.zeros_like(s))
+        return inv / inv.sum(-1, keepdim=True).clamp_min(1e-6)
 
     def _sub_params(self, params):
         K = len(self.submodules)
@@ -192,7 +205,7 @@ class MetaContainer(MetaModule):
         sub_params = self._sub_params(params)
         if active_module is not None:
             return self.submodules[active_module](x, params=sub_params[active_module])
-        if not self.uses_grad(params) and all(s._fusable for s in self.submodules):
+        if not self.uses_grad(params) and not wants_grad(x) and all(s._fusable for s in self.submodules):
             specs, routing = self.expert_specs(params), self.routing_spec()
             return ops.field_fwd(x, specs, routing, packed=self.packed_weights(specs, routing, None, params))
         weights, hard = self._routing(x[:, :3])
@@ -216,7 +229,7 @@ class MetaContainer(MetaModule):
         if d.dim() not in (2, 3):
             raise ValueError(f"background_color expects (N,3) or (B,N,3), got {tuple(d.shape)}")
         shape = d.shape
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.bg_mlp.parameters()):
+        if wants_grad(d, *self.bg_mlp.parameters()):
             from .ray_rendering import _second_order
             if d.is_cuda and not d.requires_grad and not _second_order():
                 try:

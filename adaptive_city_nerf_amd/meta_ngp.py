@@ -18,15 +18,11 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .encodings import FrequencyEncoder, HashGridEncoder, SHEncoder
+from .encodings import FrequencyEncoder, HashGridEncoder, SHEncoder, wants_grad
 from .nerfacc import OccGridEstimator
 from .metamodule import MetaLayerBlock, MetaLinear, MetaModule, MetaSequential
 from .scene_box import SceneBox
 from .trunc_exp import trunc_exp
-
-
-def _needs_grad(*ts) -> bool:
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
 class MetaNGP(MetaModule):
@@ -138,7 +134,9 @@ class MetaNGP(MetaModule):
         return self.xyz_encoder(self._world_to_unit(x_world))
 
     def _enc_dir(self, d: Tensor) -> Tensor:
-        d = d / d.norm(dim=-1, keepdim=True).clamp_min_(1e-9)
+        n = d.norm(dim=-1, keepdim=True)
+        # in place unless the directions are differentiated (norm's backward reads its own output)
+        d = d / (n.clamp_min(1e-9) if wants_grad(d) else n.clamp_min_(1e-9))
         return self.dir_encoder(d)
 
     # ------------------------------------------------------------------ fused-path plumbing
@@ -203,7 +201,7 @@ class MetaNGP(MetaModule):
 
     def uses_grad(self, params: Optional[Dict[str, Tensor]] = None) -> bool:
         tensors = [self.xyz_encoder.hash_table] + list(self._mlp_tensors(params).values())
-        return _needs_grad(*tensors)
+        return wants_grad(*tensors)
 
     # ------------------------------------------------------------------ network calls
     def color(self, d: Tensor, geo_feat: Tensor, params: Optional[Dict[str, Tensor]] = None) -> Tensor:
@@ -214,7 +212,7 @@ class MetaNGP(MetaModule):
 
     def density(self, x: Tensor, params: Optional[Dict[str, Tensor]] = None,
                 return_feats: bool = False) -> Union[Tensor, Dict[str, Tensor]]:
-        if not return_feats and x.is_cuda and self._fusable and not self.uses_grad(params):
+        if not return_feats and x.is_cuda and self._fusable and not self.uses_grad(params) and not wants_grad(x):
             # no autograd (occupancy updates / marching visibility): the fused field kernel; the
             # direction input only feeds the colour branch, whose output is dropped
             flat = x.reshape(-1, 3)
@@ -230,12 +228,14 @@ class MetaNGP(MetaModule):
 
     def _fused_train_ok(self, x: Tensor) -> bool:
         from .ray_rendering import _second_order
-        return x.is_cuda and self._fusable and x.dtype == torch.float32 and not _second_order()
+        # _FusedMLPFn has no gradient for the SH features: differentiated inputs take the composed chain
+        return (x.is_cuda and self._fusable and x.dtype == torch.float32 and not _second_order()
+                and not wants_grad(x))
 
     def forward(self, x_d: Tensor, params=None) -> Tensor:
         """[xyz(3), dir(3)] -> [rgb(3), sigma(1)] (meta_ngp.py:226-241)."""
         assert x_d.shape[-1] == 6, f"Expected (...,6) [xyz,dir], got {x_d.shape}"
-        if self._fusable and not self.uses_grad(params):
+        if self._fusable and not self.uses_grad(params) and not wants_grad(x_d):
             from ._lib import acn_routing
             r = acn_routing()
             r.K, r.cluster_2d, r.boundary_margin = 1, 1, 1.0

@@ -98,6 +98,40 @@ def hashgrid_bwd(x01: torch.Tensor, grad_out: torch.Tensor, resolutions: Sequenc
     return gt
 
 
+def hashgrid_bwd_input(x01: torch.Tensor, grad_out: torch.Tensor, table: torch.Tensor, resolutions: Sequence[int],
+                       log2T: int, F: int, interp: int) -> torch.Tensor:
+    """Gradient of hashgrid_fwd in the points, (..., 3) fp32 (acn_hashgrid_bwd_input): no atomics, bitwise
+    reproducible, each point's result independent of the batch around it.  Nearest gives zeros."""
+    require_hip(x01, "HashGridEncoder")
+    assert x01.shape[-1] == 3, f"Expected (...,3), got {tuple(x01.shape)}"
+    L = len(resolutions)
+    x = _f32(x01).view(-1, 3)
+    g = _f32(grad_out).view(-1, L * F)
+    tab = _f32(table)
+    if tab.shape != (L << log2T, F):
+        raise AcnError(f"hash table must be ({L << log2T}, {F}), got {tuple(tab.shape)}")
+    if g.shape[0] != x.shape[0]:
+        raise AcnError(f"grad_out must be ({x.shape[0]}, {L * F}), got {tuple(g.shape)}")
+    gx = torch.empty(x.shape[0], 3, device=x.device, dtype=torch.float32)
+    res = (C.c_int32 * L)(*[int(r) for r in resolutions])
+    check(_lib.lib().acn_hashgrid_bwd_input(ptr(x), x.shape[0], ptr(g), ptr(tab), res, L, log2T, F, interp, ptr(gx),
+                                            stream_of(x)), "acn_hashgrid_bwd_input")
+    return gx.view(*x01.shape[:-1], 3)
+
+
+def sh_bwd(d: torch.Tensor, g_out: torch.Tensor, levels: int) -> torch.Tensor:
+    """Gradient of sh_fwd in the (unnormalised) directions, (..., 3) fp32 (acn_sh_bwd)."""
+    require_hip(d, "SHEncoder")
+    assert d.shape[-1] == 3, f"Expected (...,3); got {tuple(d.shape)}"
+    x = _f32(d).view(-1, 3)
+    g = _f32(g_out).view(-1, levels * levels)
+    if g.shape[0] != x.shape[0]:
+        raise AcnError(f"g_out must be ({x.shape[0]}, {levels * levels}), got {tuple(g.shape)}")
+    gd = torch.empty(x.shape[0], 3, device=x.device, dtype=torch.float32)
+    check(_lib.lib().acn_sh_bwd(ptr(x), x.shape[0], levels, ptr(g), ptr(gd), stream_of(x)), "acn_sh_bwd")
+    return gd.view(*d.shape[:-1], 3)
+
+
 def sh_fwd(d: torch.Tensor, levels: int) -> torch.Tensor:
     require_hip(d, "SHEncoder")
     assert d.shape[-1] == 3, f"Expected (...,3); got {tuple(d.shape)}"

@@ -27,6 +27,7 @@ from torch import Tensor
 
 from . import nerfacc, occ_ops, ops
 from ._lib import acn_routing
+from .encodings import wants_grad
 from .meta_container import MetaContainer
 from .meta_ngp import MetaNGP
 from .ray_sampling import clamp_rays_near_far, get_ray_directions, get_rays  # noqa: F401  (re-export)
@@ -360,11 +361,17 @@ def _fused_background(model, bg_color_default: str, N: int, device):
 
 def render_rays_stratified(model, rays: Tensor, ray_samples: int, params=None, active_module: Optional[int] = None,
                            bg_color_default: str = "white", chunk: int = 1_000_000, sigma_scale=1.0, **kwargs):
-    """Stratified renderer: rgb (N,3), depth (N,), weights (N,S), acc (N,) (:290-345)."""
+    """Stratified renderer: rgb (N,3), depth (N,), weights (N,S), acc (N,) (:290-345).
+
+    Rays that require grad take the composed path (no fused render, sampler or routed pair kernels): the
+    gradient reaches the origins and directions, ``rays[:, :6]``, through the sample points, the field's
+    HIP input gradients and the compositing.  ``stratified_t_vals`` is a no-grad function, so the t-values
+    are constants: the near / far columns get a zero gradient."""
+    diff_rays = wants_grad(rays)
     tau = float(kwargs.get("early_stop_tau", 0.0))
     want_weights = bool(kwargs.get("_want_weights", True))  # render_image drops the (N,S) weights
     N = rays.shape[0]
-    if rays.is_cuda:
+    if rays.is_cuda and not diff_rays:
         fe = _fused_experts(model, params, active_module)
         fb = _fused_background(model, bg_color_default, N, rays.device) if fe is not None else None
         if fe is not None and fb is not None:
@@ -381,7 +388,7 @@ def render_rays_stratified(model, rays: Tensor, ray_samples: int, params=None, a
                                                        packed=packed, want_weights=want_weights)
             return (rgb.to(rays.dtype), depth.to(rays.dtype), None if w is None else w.to(rays.dtype),
                     acc.to(rays.dtype))
-    sub = _train_expert(model, active_module) if FUSED_TRAIN_SAMPLER else None
+    sub = _train_expert(model, active_module) if FUSED_TRAIN_SAMPLER and not diff_rays else None
     if sub is not None and rays.is_cuda and rays.dtype == torch.float32 and sub._fused_train_ok(rays):
         # differentiable single-expert path (training, inner loops): one sampler launch (t-values,
         # unit-box points, SH), the HIP hash grid under autograd and the fused MLP -- the same values
@@ -422,7 +429,7 @@ def render_rays_stratified(model, rays: Tensor, ray_samples: int, params=None, a
         if order is None:
             return out
         return tuple(None if x is None else x.index_select(0, inv) for x in out)   # the caller's order
-    if _routed_train_ok(model, rays, active_module):
+    if not diff_rays and _routed_train_ok(model, rays, active_module):
         return _render_routed(model, rays, ray_samples, params, kwargs.get("jitter_u"), bg_color_default,
                               sigma_scale)
     # composed (differentiable) path -- same structure as the reference
@@ -487,6 +494,12 @@ def _empty_occ_result(model, rays, d, params, N, bg_color_default):
     return bg_rgb, acc.clone(), weights, acc
 
 
+def _no_ray_grad(rays: Tensor) -> None:
+    if wants_grad(rays):
+        raise ops.AcnError("the occupancy renderer has no gradient for its rays (marching is a no-grad step); "
+                           "differentiate rays through render_rays_stratified")
+
+
 def _composite_packed(model, rays, d, params, ri, t0, t1, starts, counts, sigma, rgb, t_mid, N, bg_color_default):
     """nerfacc compositing of packed samples under autograd (training path)."""
     if _second_order():
@@ -507,6 +520,7 @@ def render_expert_occ(model, rays: Tensor, *, params=None, bg_color_default: str
                       render_step_size=None, alpha_thre=None, cone_angle=None, **kwargs):
     """One expert over its occupancy grid: rgb (N,3), depth (N,), weights (M,1), acc (N,)
     (ray_rendering.py:467-558).  Eval: marching + ONE fused HIP render over the packed samples."""
+    _no_ray_grad(rays)
     N = rays.shape[0]
     o, d = rays[:, :3], rays[:, 3:6]
     if getattr(model, "occ_grid", None) is None:
@@ -546,6 +560,7 @@ def render_rays_occ(model, rays: Tensor, *, params=None, bg_color_default: str =
     ``_routing`` rejects (``assert pts.dim() == 2``, meta_container.py:111), so its container path
     raises AssertionError whenever it runs; this build routes the (M, 3) midpoints, the evident
     intent (documented in DESIGN.md)."""
+    _no_ray_grad(rays)
     N = rays.shape[0]
     o, d = rays[:, :3], rays[:, 3:6]
     if active_module is not None:

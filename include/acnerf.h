@@ -99,6 +99,24 @@ int acn_hashgrid_bwd(const float* x01, int64_t M, const float* grad_out, const i
  * -> out (M, levels^2), levels in [1, 5].                                                     */
 int acn_sh_fwd(const float* d, int64_t M, int levels, float* out, void* stream);
 
+/* Gradient of acn_hashgrid_fwd in the points: the autograd of models/encodings.py:331-381 in x.
+ * grad_x (M,3) = d sum(out * grad_out) / d x01, overwritten (not accumulated):
+ *   grad_x[a] = sum_l res_l * dw_a * sum_f grad_out[l,f] * d/dw_a interp(rows_f; w),
+ * dw = 1 (Linear) or 6 w (1 - w) (Smoothstep); Nearest writes exact zeros.  The cells and weights
+ * are the forward's float32 ones.  No atomics: a point's levels are summed in a fixed order, so
+ * results repeat bit for bit and do not depend on M or on the other points.  Any L in [1, 32],
+ * F >= 1; F == 2 with a table of at most 2 GiB gathers through a buffer resource with 32-bit row
+ * offsets, every other case through 64-bit row addresses.  M == 0 is a no-op.                  */
+int acn_hashgrid_bwd_input(const float* x01, int64_t M, const float* grad_out, const float* table,
+                           const int32_t* res, int L, int log2T, int F, int interp, float* grad_x,
+                           void* stream);
+
+/* Gradient of acn_sh_fwd in the unnormalised directions: the autograd of models/encodings.py:133-151
+ * (components :27-81 differentiated as written, then n = d / max(|d|, 1e-9) as torch differentiates
+ * norm and clamp_min: g_d = (g_n - n (n.g_n)) / |d| for |d| >= 1e-9, else g_n / 1e-9).
+ * g_out (M, levels^2) -> g_d (M,3), overwritten; levels in [1, 5] (levels == 1 gives zeros).     */
+int acn_sh_bwd(const float* d, int64_t M, int levels, const float* g_out, float* g_d, void* stream);
+
 /* Bytes of device workspace the fused field / render entry points need for K experts. */
 size_t acn_workspace_bytes(int K);
 
