@@ -199,34 +199,17 @@ __device__ __forceinline__ void sh_components_bwd(float x, float y, float z, con
 // One level of HashGridEncoder._torch_forward split in two halves so that callers can keep the
 // gathers of several levels in flight: hash_issue computes the 8 corner rows and issues their
 // loads, hash_finish interpolates once they have landed.  Same arithmetic as hash_level_f2.
-// 8-byte table-row load with a cache policy: 0 plain, 1 non-temporal (nt), 2 L1-bypassing
-// (relaxed agent-scope atomic load -> global_load_dwordx2 sc1, served by the L2)
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-template <int POL>
-__device__ __forceinline__ float2 ld_row(const float2* p) {
-    if (POL == 1) {
-        const f32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x2_t*>(p));
-        return make_float2(v[0], v[1]);
-    }
-    if (POL == 2) {
-        const uint64_t u = __hip_atomic_load(reinterpret_cast<const uint64_t*>(p), __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-        return make_float2(__uint_as_float((uint32_t)u), __uint_as_float((uint32_t)(u >> 32)));
-    }
-    return *p;
-}
-
 struct HashPending {
     float2 f[8];
     float wx, wy, wz;
 };
 
-template <int INTERP, int POL = 0>
+template <int INTERP>
 __device__ __forceinline__ void hash_issue(const float2* __restrict__ tl, float sx, float sy, float sz,
                                            uint32_t mask, HashPending& p) {
     if (INTERP == 0) {
         const uint32_t ix = (uint32_t)(int)rintf(sx), iy = (uint32_t)(int)rintf(sy), iz = (uint32_t)(int)rintf(sz);
-        p.f[0] = ld_row<POL>(tl + ((ix ^ (iy * kP1) ^ (iz * kP2)) & mask));
+        p.f[0] = tl[(ix ^ (iy * kP1) ^ (iz * kP2)) & mask];
         return;
     }
     const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
@@ -241,53 +224,24 @@ __device__ __forceinline__ void hash_issue(const float2* __restrict__ tl, float 
         wz = (wz * wz) * (3.0f - 2.0f * wz);
     }
     const uint32_t a00 = y0 ^ z0, a01 = y0 ^ z1, a10 = y1 ^ z0, a11 = y1 ^ z1;
-#if ACN_XPAIR
-    // The x-neighbours of a (y, z) corner pair hash to rows i0 = x0^a and i1 = x1^a.  For even x0,
-    // i1 = i0 ^ 1: both rows sit in ONE 16-byte block, fetched by a single dwordx4 gather; only
-    // lanes with odd x0 issue a second (dwordx2) gather for i1.
-    const bool xodd = (x0 & 1u) != 0u;
-    const uint32_t aa[4] = {a00, a01, a10, a11};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const uint32_t i0 = (x0 ^ aa[c]) & mask;
-        const float4 q = *reinterpret_cast<const float4*>(tl + (i0 & ~1u));
-        const bool hi = (i0 & 1u) != 0u;
-        p.f[2 * c] = hi ? make_float2(q.z, q.w) : make_float2(q.x, q.y);
-        p.f[2 * c + 1] = hi ? make_float2(q.x, q.y) : make_float2(q.z, q.w);
-    }
-    if (xodd) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) p.f[2 * c + 1] = tl[(x1 ^ aa[c]) & mask];
-    }
-#else
-#if ACN_DIAG_HALF_CORNERS  // diagnostic build only: 4 gathers per level (wrong values)
-    p.f[0] = ld_row<POL>(tl + ((x0 ^ a00) & mask));
-    p.f[2] = ld_row<POL>(tl + ((x0 ^ a01) & mask));
-    p.f[4] = ld_row<POL>(tl + ((x0 ^ a10) & mask));
-    p.f[6] = ld_row<POL>(tl + ((x0 ^ a11) & mask));
-    p.f[1] = p.f[0]; p.f[3] = p.f[2]; p.f[5] = p.f[4]; p.f[7] = p.f[6];
-#else
-    p.f[0] = ld_row<POL>(tl + ((x0 ^ a00) & mask));
-    p.f[1] = ld_row<POL>(tl + ((x1 ^ a00) & mask));
-    p.f[2] = ld_row<POL>(tl + ((x0 ^ a01) & mask));
-    p.f[3] = ld_row<POL>(tl + ((x1 ^ a01) & mask));
-    p.f[4] = ld_row<POL>(tl + ((x0 ^ a10) & mask));
-    p.f[5] = ld_row<POL>(tl + ((x1 ^ a10) & mask));
-    p.f[6] = ld_row<POL>(tl + ((x0 ^ a11) & mask));
-    p.f[7] = ld_row<POL>(tl + ((x1 ^ a11) & mask));
-#endif
-#endif
+    p.f[0] = tl[(x0 ^ a00) & mask];
+    p.f[1] = tl[(x1 ^ a00) & mask];
+    p.f[2] = tl[(x0 ^ a01) & mask];
+    p.f[3] = tl[(x1 ^ a01) & mask];
+    p.f[4] = tl[(x0 ^ a10) & mask];
+    p.f[5] = tl[(x1 ^ a10) & mask];
+    p.f[6] = tl[(x0 ^ a11) & mask];
+    p.f[7] = tl[(x1 ^ a11) & mask];
     p.wx = wx;
     p.wy = wy;
     p.wz = wz;
 }
 
-// FMA: c = fma(f1, w, f0 * (1 - w)) (one rounding fewer than the reference's f0*(1-w) + f1*w; used
-// by the fused field, whose outputs are compared within tolerance)
-#ifndef ACN_HASH_PK
-#define ACN_HASH_PK 1   // hash_finish on packed fp32 vectors (render.hip is built without the SLP vectorizer)
-#endif
-template <int INTERP, bool FMA = false>
+// Both features at once on packed fp32 (v_pk_mul_f32 / v_pk_add_f32: per-component IEEE, the reference's
+// f0*(1-w) + f1*w roundings), written as vectors so the packing needs no SLP pass.
+// f index: bit0 = x1, bit1 = z1, bit2 = y1 (issue order above)
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+template <int INTERP>
 __device__ __forceinline__ void hash_finish(const HashPending& p, float& o0, float& o1) {
     if (INTERP == 0) {
         o0 = p.f[0].x;
@@ -296,45 +250,19 @@ __device__ __forceinline__ void hash_finish(const HashPending& p, float& o0, flo
     }
     const float wx = p.wx, wy = p.wy, wz = p.wz;
     const float ax = 1.0f - wx, ay = 1.0f - wy, az = 1.0f - wz;
-#if ACN_HASH_PK
-    if (!FMA) {   // both features at once on packed fp32 (v_pk_mul_f32 / v_pk_add_f32: per-component IEEE, the same
-                  // roundings as the scalar chain below), written as vectors so the packing needs no SLP pass
-        auto v2 = [](float2 f) { return f32x2_t{f.x, f.y}; };
-        auto lerp2 = [](f32x2_t a, f32x2_t b, float w, float aw) {
-            return a * f32x2_t{aw, aw} + b * f32x2_t{w, w};
-        };
-        const f32x2_t c00 = lerp2(v2(p.f[0]), v2(p.f[1]), wx, ax);
-        const f32x2_t c01 = lerp2(v2(p.f[2]), v2(p.f[3]), wx, ax);
-        const f32x2_t c10 = lerp2(v2(p.f[4]), v2(p.f[5]), wx, ax);
-        const f32x2_t c11 = lerp2(v2(p.f[6]), v2(p.f[7]), wx, ax);
-        const f32x2_t c0 = lerp2(c00, c10, wy, ay);
-        const f32x2_t c1 = lerp2(c01, c11, wy, ay);
-        const f32x2_t o = lerp2(c0, c1, wz, az);
-        o0 = o[0];
-        o1 = o[1];
-        return;
-    }
-#endif
-    auto lerp = [&](float a, float b, float w, float aw) { return FMA ? fmaf(b, w, a * aw) : a * aw + b * w; };
-    // f index: bit0 = x1, bit1 = z1, bit2 = y1 (issue order above)
-    {
-        const float c00 = lerp(p.f[0].x, p.f[1].x, wx, ax);
-        const float c01 = lerp(p.f[2].x, p.f[3].x, wx, ax);
-        const float c10 = lerp(p.f[4].x, p.f[5].x, wx, ax);
-        const float c11 = lerp(p.f[6].x, p.f[7].x, wx, ax);
-        const float c0 = lerp(c00, c10, wy, ay);
-        const float c1 = lerp(c01, c11, wy, ay);
-        o0 = lerp(c0, c1, wz, az);
-    }
-    {
-        const float c00 = lerp(p.f[0].y, p.f[1].y, wx, ax);
-        const float c01 = lerp(p.f[2].y, p.f[3].y, wx, ax);
-        const float c10 = lerp(p.f[4].y, p.f[5].y, wx, ax);
-        const float c11 = lerp(p.f[6].y, p.f[7].y, wx, ax);
-        const float c0 = lerp(c00, c10, wy, ay);
-        const float c1 = lerp(c01, c11, wy, ay);
-        o1 = lerp(c0, c1, wz, az);
-    }
+    auto v2 = [](float2 f) { return f32x2_t{f.x, f.y}; };
+    auto lerp2 = [](f32x2_t a, f32x2_t b, float w, float aw) {
+        return a * f32x2_t{aw, aw} + b * f32x2_t{w, w};
+    };
+    const f32x2_t c00 = lerp2(v2(p.f[0]), v2(p.f[1]), wx, ax);
+    const f32x2_t c01 = lerp2(v2(p.f[2]), v2(p.f[3]), wx, ax);
+    const f32x2_t c10 = lerp2(v2(p.f[4]), v2(p.f[5]), wx, ax);
+    const f32x2_t c11 = lerp2(v2(p.f[6]), v2(p.f[7]), wx, ax);
+    const f32x2_t c0 = lerp2(c00, c10, wy, ay);
+    const f32x2_t c1 = lerp2(c01, c11, wy, ay);
+    const f32x2_t o = lerp2(c0, c1, wz, az);
+    o0 = o[0];
+    o1 = o[1];
 }
 
 // Buffer-resource form of hash_issue/hash_finish (Linear/Smoothstep).  The x-neighbours of a
@@ -342,9 +270,6 @@ __device__ __forceinline__ void hash_finish(const HashPending& p, float& o0, flo
 // 16-byte gather of the aligned block holding i0 returns both.  The second gather (8 bytes, row
 // i1) is only needed by lanes with odd x0: the other lanes pass an out-of-range offset, which the
 // buffer's range check turns into a no-op (no cache access).
-#ifndef ACN_XPAIR_NOSKIP
-#define ACN_XPAIR_NOSKIP 0
-#endif
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 struct HashPendingX {
@@ -377,63 +302,15 @@ __device__ __forceinline__ void hash_issue_x(__amdgpu_buffer_rsrc_t rs, uint32_t
         sel |= (i0 & 1u) << c;
         p.q[c] = __builtin_amdgcn_raw_buffer_load_b128(rs, lvbase + ((i0 & ~1u) << 3), 0, 0);
     }
-#if ACN_DIAG_X4ONLY  // diagnostic build only: no second gather (wrong values for odd x0)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) p.r[c] = u32x2_t{0u, 0u};
-#else
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const uint32_t i1 = (x1 ^ aa[c]) & mask;
-        p.r[c] = __builtin_amdgcn_raw_buffer_load_b64(rs, (xodd || ACN_XPAIR_NOSKIP) ? lvbase + (i1 << 3) : 0xFFFFFFF0u, 0, 0);
+        p.r[c] = __builtin_amdgcn_raw_buffer_load_b64(rs, xodd ? lvbase + (i1 << 3) : 0xFFFFFFF0u, 0, 0);
     }
-#endif
     p.wx = wx;
     p.wy = wy;
     p.wz = wz;
     p.sel = sel;
-}
-
-// Buffer-resource form of hash_issue, one 8-byte gather per corner (the render's default, ACN_XPAIR == 3): the
-// row offsets are 32-bit (lvbase + 8 * row from the expert's table base in the resource), so no 64-bit address
-// is formed per corner.  The gathers of the global-address form (hash_issue) returned a wrong row to lanes 48-63
-// of one level now and then inside the render kernels; this form never did.
-template <int INTERP>
-__device__ __forceinline__ void hash_issue_b(__amdgpu_buffer_rsrc_t rs, uint32_t lvbase, float sx, float sy, float sz,
-                                             uint32_t mask, HashPending& p) {
-    auto ld = [&](uint32_t row) {
-        const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, lvbase + (row << 3), 0, 0);
-        return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
-    };
-    if (INTERP == 0) {
-        const uint32_t ix = (uint32_t)(int)rintf(sx), iy = (uint32_t)(int)rintf(sy), iz = (uint32_t)(int)rintf(sz);
-        p.f[0] = ld((ix ^ (iy * kP1) ^ (iz * kP2)) & mask);
-        return;
-    }
-    const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
-    float wx = sx - fx, wy = sy - fy, wz = sz - fz;
-    const uint32_t x0 = (uint32_t)(int)fx;
-    const uint32_t y0 = (uint32_t)(int)fy * kP1, y1 = y0 + kP1;
-    const uint32_t z0 = (uint32_t)(int)fz * kP2, z1 = z0 + kP2;
-    const uint32_t x1 = x0 + 1u;
-    if (INTERP == 2) {   // the constants offset by an opaque +0.0f: formed here, not hoisted into VGPR pairs
-        float k3 = 3.0f, k2 = 2.0f;
-        asm volatile("" : "+s"(k3), "+s"(k2));
-        wx = (wx * wx) * (k3 - k2 * wx);
-        wy = (wy * wy) * (k3 - k2 * wy);
-        wz = (wz * wz) * (k3 - k2 * wz);
-    }
-    const uint32_t a00 = y0 ^ z0, a01 = y0 ^ z1, a10 = y1 ^ z0, a11 = y1 ^ z1;
-    p.f[0] = ld((x0 ^ a00) & mask);
-    p.f[1] = ld((x1 ^ a00) & mask);
-    p.f[2] = ld((x0 ^ a01) & mask);
-    p.f[3] = ld((x1 ^ a01) & mask);
-    p.f[4] = ld((x0 ^ a10) & mask);
-    p.f[5] = ld((x1 ^ a10) & mask);
-    p.f[6] = ld((x0 ^ a11) & mask);
-    p.f[7] = ld((x1 ^ a11) & mask);
-    p.wx = wx;
-    p.wy = wy;
-    p.wz = wz;
 }
 
 // The 8 corner rows of a landed hash_issue_x, in hash_issue's order (f index: bit0 = x1, bit1 = z1, bit2 = y1), for
@@ -630,53 +507,10 @@ __device__ __forceinline__ float tval(float near, float far, int s, int S, const
     return lo + (hi - lo) * jit[s];
 }
 
-// ---- VALU -> MFMA operand fence (round 5; OFF by default since round 6, §4l).  Round 5 took the
-// rare run-to-run differences of the renders (16 columns of one MFMA tile) for stale fp16 B operands and put every
-// B fragment through ONE asm statement holding 16 wait states.  Round 6 found their cause elsewhere: the hash-table
-// gathers, issued as global loads from 64-bit addresses, now and then returned a wrong row to lanes 48-63 of one
-// level (self-check records of the hash features); with the gathers on buffer loads the field repeats, the slots
-// self-check builds and the training-MLP repeats show no difference with or without the fence, and hipcc's own
-// padding (>= 2 wait states; the box probe needs 1) holds in every kernel (tests/test_hazard_audit.py).  The fence
-// cost the meta step 5%, so it is compiled out; -DACN_OPND_FENCE_ON restores it for A/B runs.
+// fp16 MFMA operand fragment.  Round 5 took rare run-to-run differences of the renders for stale fp16 B operands and
+// put every fragment through a VALU -> MFMA operand fence (16 wait states in one asm statement); round 6 found the
+// cause in the hash gathers issued as global loads and removed the fence, which cost the meta step 5% and changed
+// nothing (hipcc's own padding is audited by tests/test_hazard_audit.py).
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-#ifdef ACN_OPND_FENCE_ON
-#define ACN_OPND_PAD "s_nop 7\n\ts_nop 7"
-#define ACN_OPND_SB0 __builtin_amdgcn_sched_barrier(0);
-#define ACN_OPND_ASM(...) asm volatile(__VA_ARGS__)
-#else
-#define ACN_OPND_PAD ""
-#define ACN_OPND_SB0
-#define ACN_OPND_ASM(...)
-#endif
-#define ACN_OPND_CLOB
-__device__ __forceinline__ void opnd_fence(f16x8& a) { ACN_OPND_SB0 ACN_OPND_ASM(ACN_OPND_PAD : "+v"(a) : ACN_OPND_CLOB); ACN_OPND_SB0 }
-__device__ __forceinline__ void opnd_fence(f16x8& a, f16x8& b) {
-    ACN_OPND_SB0 ACN_OPND_ASM(ACN_OPND_PAD : "+v"(a), "+v"(b) : ACN_OPND_CLOB); ACN_OPND_SB0
-}
-__device__ __forceinline__ void opnd_fence(f16x8& a, f16x8& b, f16x8& c, f16x8& d) {
-    ACN_OPND_SB0 ACN_OPND_ASM(ACN_OPND_PAD : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : ACN_OPND_CLOB); ACN_OPND_SB0
-}
-__device__ __forceinline__ void opnd_fence(f16x8& a, f16x8& b, f16x8& c, f16x8& d, f16x8& e, f16x8& f, f16x8& g,
-                                           f16x8& h) {
-    ACN_OPND_SB0 ACN_OPND_ASM(ACN_OPND_PAD : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h)
-                              : ACN_OPND_CLOB); ACN_OPND_SB0
-}
-// one plane of N fragments (N = 1, 2, 4, 8)
-template <int N>
-__device__ __forceinline__ void opnd_fence_n(f16x8 (&x)[N]) {
-    static_assert(N == 1 || N == 2 || N == 4 || N == 8, "opnd_fence_n: N in {1, 2, 4, 8}");
-    if constexpr (N == 1) opnd_fence(x[0]);
-    else if constexpr (N == 2) opnd_fence(x[0], x[1]);
-    else if constexpr (N == 4) opnd_fence(x[0], x[1], x[2], x[3]);
-    else opnd_fence(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7]);
-}
-// hi and lo planes of N fragments (N = 1, 2, 4)
-template <int N>
-__device__ __forceinline__ void opnd_fence_n(f16x8 (&x)[N], f16x8 (&y)[N]) {
-    static_assert(N == 1 || N == 2 || N == 4, "opnd_fence_n: N in {1, 2, 4}");
-    if constexpr (N == 1) opnd_fence(x[0], y[0]);
-    else if constexpr (N == 2) opnd_fence(x[0], x[1], y[0], y[1]);
-    else opnd_fence(x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]);
-}
 
 }  // namespace acn

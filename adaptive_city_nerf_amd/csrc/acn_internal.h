@@ -51,7 +51,7 @@ struct ExpertMeta {
     const float* table;
     float amin[3];
     float ext[3];
-    float rext[3];   // 1 / ext (host)
+    float rext[3];   // 1 / ext (host); no kernel reads it any more -- kept so the kernarg layout stays as it was
     int32_t res[16];
 };
 

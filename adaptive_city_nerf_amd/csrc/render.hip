@@ -6,16 +6,31 @@
 //   background_color :347-382),
 //   models/inr/meta_ngp.py:155-241 MetaNGP._world_to_unit / density / color / forward.
 //
-// Execution model: one wave owns one ray at a time and walks it front to back in tiles of 32
-// samples.  Inside a tile the 64 lanes are (sample j = lane & 31, half h = lane >> 5); half h
-// hash-encodes levels 8h..8h+7 of sample j, which is exactly the B-operand layout of
-// v_mfma_f32_32x32x2_f32 for the first layer (k-step s pairs feature 16*0+s with 16*1+s).  Every
-// MLP layer is H^T = W . X^T on fp32 MFMA (exact fp32 fma chains: parity mode), with the layer's
-// accumulator registers feeding the next layer's B operand directly (no LDS round trip).  The
-// packed weights of up to two experts sit in LDS (58 KB each); more experts read them from L2.
-// Compositing uses a 32-lane exclusive prefix product of (1 - alpha + 1e-10) in double (torch's
-// CPU cumprod accumulates in double), carries transmittance across tiles, and stops the ray once
-// T < tau (early ray termination; tau = 0 disables it).
+// Field tile: 32 samples per wave; the 64 lanes are (sample j = lane & 31, half h = lane >> 5) and half h
+// hash-encodes levels 8h..8h+7 of sample j with buffer-load gathers of x-paired 16-B blocks (hash_issue_x,
+// ACN_HASH_DEPTH levels in flight).  Every MLP layer is H^T = W . X^T on v_mfma_f32_32x32x16_f16 with a 3-term
+// fp16 split of weights and activations (hi*hi + hi*lo + lo*hi, ~22 bits), the layer's accumulator registers
+// feeding the next layer's B operand directly (no LDS round trip).  The SH columns of colour layer 0 are folded
+// into a per-ray bias (fold_sh_bias).  Compositing keeps a 32-lane exclusive prefix product of
+// (1 - alpha + 1e-10) in double on DPP (torch's CPU cumprod accumulates in double), carries transmittance
+// across tiles, and stops the ray once T < tau (early ray termination; tau = 0 disables it).
+//
+// The render kernels and when acn_render_stratified_fwd_ordered / acn_render_packed_fwd launch each:
+//   render_ws_kernel     one expert, S <= 256, tau <= 0: a workgroup's 16 rays cut into depth tiles
+//   render_kernel        one expert otherwise, and routed K == 2 (both images in LDS): one wave per ray
+//   render_wss_kernel    routed K > 2, S <= 256, tau <= 0: depth tiles over two LDS expert slots
+//                        (16-ray rounds up to S = 128, else 8-ray rounds)
+//   render_slots_kernel  routed K > 2 otherwise: one wave per ray over two LDS expert slots
+//   occ_render_kernel    packed (occupancy-grid) samples: one wave per ray
+//
+// Build switches that remain (every other A/B of rounds 2-6 is settled and gone; DESIGN.md §4 keeps the figures):
+//   ACN_MLP_F16X3      0: the exact-fp32 MLP on v_mfma_f32_32x32x2_f32, the documented escape hatch
+//   ACN_XPAIR          2 (default) buffer loads of x-paired blocks; 0 global loads from 64-bit addresses, the form
+//                      that reproduced the wrong-row gathers -- the Nearest branch keeps that path
+//                      anyway, so the switch costs nothing
+//   ACN_FIELD_CHECK, ACN_SLOTS_CHECK   self-check builds for that open defect (tools/dbg/selfcheck.py), with their
+//                      acn_debug_* fetch exports
+//   ACN_HASH_DEPTH, ACN_SLOTS_THREADS  plain constants
 #include "acn_device.h"
 #include "acn_internal.h"
 
@@ -25,24 +40,10 @@ using namespace acn;
 #define ACN_MLP_F16X3 1  // MLP on v_mfma_f32_32x32x16_f16 with a 3-term fp16 split (hi*hi + hi*lo + lo*hi)
 #endif
 
-#ifndef ACN_SLOTS
-#define ACN_SLOTS 1  // routed K > 2: stage the two most needed experts per workgroup (render_slots_kernel)
-#endif
-
 #ifndef ACN_XPAIR
-#define ACN_XPAIR 2  // hash gathers: 2 buffer loads of x-paired 16-B blocks (default); 3 buffer loads,
-                     // one 8-B row per corner; 0 global loads from 64-bit addresses (round 5: wrong rows in lanes 48-63)
+#define ACN_XPAIR 2  // hash gathers: 2 buffer loads of x-paired 16-B blocks (default);
+                     // 0 global loads from 64-bit addresses (round 5: wrong rows in lanes 48-63)
 #endif
-#ifndef ACN_LEVEL_PARITY
-#define ACN_LEVEL_PARITY 0  // 1: half h encodes levels 2i+h (instruction i = two adjacent levels)
-#endif
-#ifndef ACN_FINE_POL
-#define ACN_FINE_POL 0      // load policy (ld_row) of the gathers of the finest levels
-#endif
-#ifndef ACN_FINE_FROM
-#define ACN_FINE_FROM 8     // first gather step i (0..7) that uses ACN_FINE_POL
-#endif
-
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -100,7 +101,7 @@ __device__ __forceinline__ int xrow_acc(int s, int h, int e) {
 // input = hash features: element e of k-step s of half h is feat[8s + e] of that half
 __device__ __forceinline__ int xcol_feat(int s, int h, int e) {
     const int i = 8 * s + e;
-    return ACN_LEVEL_PARITY ? 4 * (i >> 1) + 2 * h + (i & 1) : 16 * h + i;
+    return 16 * h + i;
 }
 
 __device__ float xweight(const PackSrc& p, int layer, int row, int s, int h, int e) {
@@ -148,8 +149,7 @@ __device__ float pack_value(const PackSrc& p, int idx) {
     if (ACN_MLP_F16X3 && idx < PK_WC3) return pack_value_x3(p, idx);
     if (idx < PK_W2) {  // sigma_trunk.0 (64, 32): k = 16h + s
         decode_a(idx - PK_W1, 16, t, s, i, h);
-        const int col = ACN_LEVEL_PARITY ? 4 * (s >> 1) + 2 * h + (s & 1) : 16 * h + s;
-        return p.sig_w0[(i + 32 * t) * 32 + col];
+        return p.sig_w0[(i + 32 * t) * 32 + 16 * h + s];
     }
     if (idx < PK_WH) {  // sigma_trunk.1 (64, 64): k = rho(r, h) + 32 Tin, s = 16 Tin + r
         decode_a(idx - PK_W2, 32, t, s, i, h);
@@ -254,17 +254,12 @@ __device__ __forceinline__ void split_acc2(const f32x16& a0, const f32x16& a1, f
 }
 
 // out[T] = bias + W . X over NK k-steps of 16, three fp16 products per k-step (small terms first).
-// The B fragments (bh, bl: v_cvt_pk_f16_f32 results) pass through the operand fence first (acn_device.h,
-// DESIGN.md §4j): the round-4 pad at this point (ACN_X3_NOP) was placed by position, and the compiler still
-// sank the last conversions past it into the k-step loop, 2 wait states before their MFMA.
 // REV: k-steps in reverse order (colour layer 0 with per-lane SH: the SH k-step first, the order the per-ray
 // fold accumulates in, so the result is bit-identical to fold_sh_bias + the folded layer)
 template <int NT, int NK, bool REV = false>
 __device__ __forceinline__ void layer_x3(const float* W, int seg, const float* bias_base, int bt, int lane, int h,
                                          f16x8 (&bh)[NK], f16x8 (&bl)[NK], f32x16 (&out)[NT],
                                          int nk_used = NK) {
-    if (nk_used == 1) opnd_fence(bh[REV ? NK - 1 : 0], bl[REV ? NK - 1 : 0]);
-    else opnd_fence_n<NK>(bh, bl);
 #pragma unroll
     for (int T = 0; T < NT; ++T) out[T] = bias_frag_at(bias_base, bt + T, h);
 #pragma unroll
@@ -296,7 +291,6 @@ __device__ __forceinline__ void fold_sh_bias(const float* W, const float (&shv)[
     {   // k-step 1 of the colour-layer-0 image = head rows 16..31 = this half's SH values (shv)
         f16x8 sh_hi, sh_lo;
         split8(shv, sh_hi, sh_lo);
-        opnd_fence(sh_hi, sh_lo);   // the fold had no pad at all
         const float* f0 = W + PK_WC1 + (((0 * 2 + 1) * 2) * 64 + lane) * 4;
         const float* f1 = W + PK_WC1 + (((1 * 2 + 1) * 2) * 64 + lane) * 4;
         const f16x8 h0 = ldh8(f0), l0 = ldh8(f0 + 256), h1 = ldh8(f1), l1 = ldh8(f1 + 256);
@@ -329,15 +323,10 @@ __device__ __forceinline__ void fold_sh_bias(const float* W, const float (&shv)[
     }
 }
 
-#ifndef ACN_FAST_VALU
-#define ACN_FAST_VALU 0  // 1: one-instruction ReLU (v_max_f32), FMA lerps, reciprocal world->unit
-#endif
+// compare + select, NaN-propagating like torch.relu
 __device__ __forceinline__ void relu16(f32x16& v) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i)
-        // ACN_FAST_VALU: v_max_f32 (NaN -> 0 inside the fused MLP; a NaN sample still renders NaN
-        // because its t / dist are NaN); else compare + select, NaN-propagating like torch.relu
-        v[i] = ACN_FAST_VALU ? fmaxf(v[i], 0.0f) : (v[i] < 0.0f ? 0.0f : v[i]);
+    for (int i = 0; i < 16; ++i) v[i] = v[i] < 0.0f ? 0.0f : v[i];
 }
 
 // 64 -> 64 layer: out tiles (o0, o1) = bias + W . [in0; in1].  A fragments are double
@@ -382,12 +371,9 @@ constexpr unsigned kFchkMax = 4096;
 __device__ float g_fchk_rec[40 * kFchkMax];
 __device__ unsigned g_fchk_n;
 #endif
-#if ACN_DIAG_PHASE  // diagnostic build only: per-wave timestamp taken right after the hash phase
-__shared__ uint64_t g_diag_stamp[16];
-#endif
 
 // level encoded by half h at gather step i (its features sit at feat[2i], feat[2i+1])
-__device__ __forceinline__ int level_of(int i, int h) { return ACN_LEVEL_PARITY ? 2 * i + h : i + 8 * h; }
+__device__ __forceinline__ int level_of(int i, int h) { return i + 8 * h; }
 
 // Hash-encode this half's 8 levels (encodings.py:331-381) with the gathers of ACN_HASH_DEPTH
 // levels in flight: level step i+D-1 is issued before step i is interpolated.
@@ -403,8 +389,7 @@ __device__ __forceinline__ void hash_levels8(const ExpertMeta& em, int log2T, in
         HashPendingX px[D];
         auto issue_x = [&](int i, HashPendingX& pp) {
             const int lv = level_of(i, h);
-            const float res = (float)(ACN_LEVEL_PARITY ? (h ? em.res[2 * i + 1] : em.res[2 * i])
-                                                       : (h ? em.res[8 + i] : em.res[i]));
+            const float res = (float)(h ? em.res[8 + i] : em.res[i]);
             hash_issue_x<INTERP>(rs, (uint32_t)lv << (log2T + 3), x0 * res, x1 * res, x2 * res, mask, pp);
         };
 #pragma unroll
@@ -419,25 +404,13 @@ __device__ __forceinline__ void hash_levels8(const ExpertMeta& em, int log2T, in
         return;
     }
 #endif
+    // Nearest, and every interpolation of the ACN_XPAIR == 0 build: global loads from 64-bit addresses
     HashPending pend[D];
-#if ACN_XPAIR == 3
-    // the expert's 16 level tables (F = 2) in one buffer resource: level lv starts at byte lv << (log2T + 3)
-    const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)em.table, (short)0, (int)(uint32_t)((16ull << log2T) * 8ull), 0x00020000);
-#endif
     auto issue = [&](int i, HashPending& pp) {
         const int lv = level_of(i, h);
-        const float res = (float)(ACN_LEVEL_PARITY ? (h ? em.res[2 * i + 1] : em.res[2 * i])
-                                                   : (h ? em.res[8 + i] : em.res[i]));
-#if ACN_XPAIR == 3
-        hash_issue_b<INTERP>(rsb, (uint32_t)lv << (log2T + 3), x0 * res, x1 * res, x2 * res, mask, pp);
-        return;
-#endif
+        const float res = (float)(h ? em.res[8 + i] : em.res[i]);
         const float2* tl = reinterpret_cast<const float2*>(em.table) + ((size_t)lv << log2T);
-        if (i >= ACN_FINE_FROM)
-            hash_issue<INTERP, ACN_FINE_POL>(tl, x0 * res, x1 * res, x2 * res, mask, pp);
-        else
-            hash_issue<INTERP, 0>(tl, x0 * res, x1 * res, x2 * res, mask, pp);
+        hash_issue<INTERP>(tl, x0 * res, x1 * res, x2 * res, mask, pp);
     };
 #pragma unroll
     for (int l = 0; l < D - 1; ++l) issue(l, pend[l]);
@@ -445,7 +418,7 @@ __device__ __forceinline__ void hash_levels8(const ExpertMeta& em, int log2T, in
     for (int l = 0; l < 8; ++l) {
         if (l + D - 1 < 8) issue(l + D - 1, pend[(l + D - 1) % D]);
         __builtin_amdgcn_sched_barrier(0);
-        hash_finish<INTERP, ACN_FAST_VALU != 0>(pend[l % D], feat[2 * l], feat[2 * l + 1]);
+        hash_finish<INTERP>(pend[l % D], feat[2 * l], feat[2 * l + 1]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -465,22 +438,11 @@ __device__ __forceinline__ void field_tile(const float* W, const ExpertMeta& em,
     const int h = opaque_v(lane >> 5);
     // _world_to_unit (meta_ngp.py:155-158)
     const float eps = 1e-6f, hi = 1.0f - 1e-6f;
-#if ACN_FAST_VALU  // multiply by the host-computed reciprocal extent (<= 1 ulp from the division)
-    const float x0 = clamp_nan((px - em.amin[0]) * em.rext[0], eps, hi);
-    const float x1 = clamp_nan((py - em.amin[1]) * em.rext[1], eps, hi);
-    const float x2 = clamp_nan((pz - em.amin[2]) * em.rext[2], eps, hi);
-#else
     const float x0 = clamp_nan((px - em.amin[0]) / em.ext[0], eps, hi);
     const float x1 = clamp_nan((py - em.amin[1]) / em.ext[1], eps, hi);
     const float x2 = clamp_nan((pz - em.amin[2]) / em.ext[2], eps, hi);
-#endif
     float feat[16];
-#if ACN_DIAG_NOHASH  // diagnostic build only: no gathers
-#pragma unroll
-    for (int i = 0; i < 16; ++i) feat[i] = x0 * (float)(i + 1) - x1 + x2 * (float)i;
-#else
     hash_levels8<INTERP>(em, log2T, h, x0, x1, x2, feat);
-#endif
 #if ACN_FIELD_CHECK  // diagnostic build only: the hash encoding evaluated twice; differing lanes are counted
     if constexpr (FCHK) {
         float f2[16];
@@ -506,21 +468,6 @@ __device__ __forceinline__ void field_tile(const float* W, const ExpertMeta& em,
                 for (int i = 0; i < 16; ++i) { o[8 + i] = feat[i]; o[24 + i] = f2[i]; }
             }
         }
-    }
-#endif
-#if ACN_DIAG_PHASE
-    {
-        const uint64_t tnow = __builtin_amdgcn_s_memtime();
-        if (lane == 0) g_diag_stamp[threadIdx.x >> 6] = tnow;
-    }
-#endif
-#if ACN_DIAG_NOMLP  // diagnostic build only: no MLP
-    {
-        float a = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) a += feat[i];
-        rr = a; rg = feat[1]; rb = feat[2]; sraw = __shfl(feat[3], lane & 31);
-        return;
     }
 #endif
 #if ACN_MLP_F16X3
@@ -801,9 +748,6 @@ struct RayAcc {
     float r, g, b, d, a;
 };
 
-#ifndef ACN_COMPOSITE_DPP
-#define ACN_COMPOSITE_DPP 1
-#endif
 // a double moved by one DPP control (both 32-bit halves); lanes without a source (or outside ROWMASK)
 // get the multiplicative identity 1.0
 template <int CTRL, int ROWMASK>
@@ -824,17 +768,11 @@ __device__ __forceinline__ double dpp_add_f64(double v) {
     return v + __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 __device__ __forceinline__ double wave32_sum(double v) {
-#if ACN_COMPOSITE_DPP
     v = dpp_add_f64<0xB1>(v);   // quad_perm [1,0,3,2]
     v = dpp_add_f64<0x4E>(v);   // quad_perm [2,3,0,1]
     v = dpp_add_f64<0x141>(v);  // row_half_mirror
     v = dpp_add_f64<0x140>(v);  // row_mirror
     return lane_f64(v, 0) + lane_f64(v, 16);
-#else
-#pragma unroll
-    for (int off = 16; off >= 1; off >>= 1) v += __shfl_xor(v, off, 32);
-    return v;
-#endif
 }
 
 __device__ __forceinline__ void composite_tile(RayAcc& acc, bool valid, float cr, float cg, float cb, float sig,
@@ -846,7 +784,6 @@ __device__ __forceinline__ void composite_tile(RayAcc& acc, bool valid, float cr
     float x = (1.0f - alpha) + 1e-10f;
     if (!valid) { x = 1.0f; alpha = 0.0f; }
     double incl = (double)x;
-#if ACN_COMPOSITE_DPP
     // inclusive product over the 32 samples of each lane half on DPP (no LDS): row_shr 1/2/4/8 inside
     // each 16-lane row, then row_bcast:15 carries row 0's (row 2's) product into row 1 (row 3); lanes
     // without a source keep the identity 1.0.  Both halves hold the same samples, so lane 31 = lane 63.
@@ -857,15 +794,6 @@ __device__ __forceinline__ void composite_tile(RayAcc& acc, bool valid, float cr
     incl *= dpp_f64<0x142, 0xA>(incl);
     double excl = dpp_f64<0x138, 0xF>(incl);  // wave_shr:1
     if (j == 0) excl = 1.0;
-#else
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-        const double y = __shfl_up(incl, off, 32);
-        if (j >= off) incl *= y;
-    }
-    double excl = __shfl_up(incl, 1, 32);
-    if (j == 0) excl = 1.0;
-#endif
     const float Ts = (float)(acc.T * excl);
     const float w = alpha * Ts;
     if (wout) *wout = w;
@@ -876,11 +804,7 @@ __device__ __forceinline__ void composite_tile(RayAcc& acc, bool valid, float cr
         acc.d += w * t;
         acc.a += w;
     }
-#if ACN_COMPOSITE_DPP
     acc.T = acc.T * lane_f64(incl, 31);
-#else
-    acc.T = acc.T * __shfl(incl, 31, 32);
-#endif
 }
 
 __device__ __forceinline__ void finish_ray(const RayAcc& acc, float& r, float& g, float& b, float& d, float& a) {
@@ -917,7 +841,6 @@ __device__ __forceinline__ void background(const BgArgs& bg, float dx, float dy,
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float v = lane < bg.hidden ? hv * bg.w2[c * bg.hidden + lane] : 0.0f;
-#if ACN_COMPOSITE_DPP
         v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
         v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
         v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
@@ -926,10 +849,6 @@ __device__ __forceinline__ void background(const BgArgs& bg, float dx, float dy,
              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16))) +
             (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)) +
              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48)));
-#else
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-#endif
         out[c] = sigmoidf_(v + bg.b2[c]);
     }
 }
@@ -947,10 +866,6 @@ struct RenderParams {
                            // split routed render); NULL = N
 };
 
-#ifndef ACN_SHFOLD
-#define ACN_SHFOLD 1
-#endif
-
 // t of sample i without jitter, branch-free (same roundings as lin01/tlin)
 __device__ __forceinline__ float tlin_sel(float near, float far, int i, int S, float step) {
     const float a = fmaf(step, (float)i, 0.0f);
@@ -959,95 +874,45 @@ __device__ __forceinline__ float tlin_sel(float near, float far, int i, int S, f
     return near * (1.0f - u) + far * u;
 }
 
-#ifndef ACN_SLOTS_PROF
-#define ACN_SLOTS_PROF 0   // diagnostic build: per-ray section stamps of render_slots_kernel (acn_debug_slprof_fetch)
-#endif
-#if ACN_SLOTS_PROF
-constexpr int kSlProfRays = 1 << 20;
-__device__ unsigned long long g_slprof[kSlProfRays * 6];
-#define SL_MARK(ray, i) if (lane == 0 && (ray) < kSlProfRays) g_slprof[(ray) * 6 + (i)] = wall_clock64();
-#else
-#define SL_MARK(ray, i)
-#endif
-// One ray, front to back in 32-sample tiles: t-values -> field(px, py, pz, shv, folded, y...) ->
-// volume_render conditioning -> compositing -> background -> outputs.  `field` evaluates the
-// (routed) container for this lane's sample; it is a template callable so the single-expert, the
-// LDS-resident and the slot-staged kernels share this body.
-template <class FieldFn>
-__device__ __forceinline__ void render_ray(const RenderParams& p, const BgArgs& bg, int64_t ray, int lane, float step,
-                                           FieldFn&& field) {
-    const int j = lane & 31, h = lane >> 5;
-    const int S = p.S;
-#if ACN_DIAG_CLOCK || ACN_DIAG_PHASE
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#endif
-#if ACN_DIAG_CLOCK  // diagnostic build only: depth[ray] <- in-kernel shader clock (MHz) over the ray
-    const uint64_t diag_t0 = __builtin_amdgcn_s_memtime(), diag_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#if ACN_DIAG_WAVETIME  // diagnostic build only: rgb[ray] <- bit patterns of (start, end) 100-MHz stamps, HW ids
-    const uint32_t diag_w0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
-#endif
+// One ray's inputs: origin, direction, near / far and its jitter row (NULL: eval, no jitter)
+struct RayIn {
+    float ox, oy, oz, dx, dy, dz, near, far;
+    const float* jit;
+};
+__device__ __forceinline__ RayIn load_ray(const RenderParams& p, int64_t ray) {
     const float* rp = p.rays + ray * 8;
-    const float ox = rp[0], oy = rp[1], oz = rp[2], dx = rp[3], dy = rp[4], dz = rp[5];
-    const float near = rp[6], far = rp[7];
-    const float* jit = p.jitter ? p.jitter + ray * S : nullptr;
-    float sh[16], shv[8];
-    dir_sh(dx, dy, dz, sh);
-    sh_rows_for_half(sh, h, shv);
-    uint32_t folded = 0u;
-#if ACN_DIAG_PHASE
-    uint32_t dg_hash = 0u, dg_mlp = 0u, dg_comp = 0u, dg_n = 0u;
-#endif
-    RayAcc acc{1.0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    int s0 = 0;
-    for (; s0 < S; s0 += 32) {
-        const int s = s0 + j;
-        const bool valid = s < S;
-        const int sc = valid ? s : S - 1;
-        float t, dist;
-        if (!jit) {  // eval: dist = t[i+1] - t[i], the last one repeated (ray_rendering.py:144-145)
-            const int i0 = sc < S - 1 ? sc : S - 2;
-            const float ta = tlin_sel(near, far, i0, S, step), tb = tlin_sel(near, far, i0 + 1, S, step);
-            t = sc < S - 1 ? ta : tb;
-            dist = tb - ta;
-        } else {
-            t = tval(near, far, sc, S, jit);
-            const float tn = (sc < S - 1) ? tval(near, far, sc + 1, S, jit) : t;
-            const float tp = (sc == S - 1 && S > 1) ? tval(near, far, sc - 1, S, jit) : t;
-            dist = (sc < S - 1) ? (tn - t) : (t - tp);
-        }
-        const float px = ox + dx * t, py = oy + dy * t, pz = oz + dz * t;
-        float yr, yg, yb, ys;
-#if ACN_DIAG_PHASE
-        const uint64_t dA = __builtin_amdgcn_s_memtime();
-#endif
-        field(sc, px, py, pz, shv, folded, yr, yg, yb, ys);
-        if (s0 == 0) { SL_MARK(ray, 3) }
-#if ACN_DIAG_PHASE
-        const uint64_t dB = __builtin_amdgcn_s_memtime();
-        const uint32_t dS = __builtin_amdgcn_readfirstlane((uint32_t)g_diag_stamp[wave]);
-        dg_hash += dS - (uint32_t)dA;
-        dg_mlp += (uint32_t)dB - dS;
-        dg_n += 1u;
-#endif
-        // volume_render input conditioning (:140-143)
-        yr = clamp_nan(yr, 0.0f, 1.0f);
-        yg = clamp_nan(yg, 0.0f, 1.0f);
-        yb = clamp_nan(yb, 0.0f, 1.0f);
-        float sig = clamp_min_nan(ys, 0.0f);
-        if (p.sigma_scale != 1.0f) sig = sig * p.sigma_scale;
-        float wv;
-        composite_tile(acc, valid, yr, yg, yb, sig, t, dist, j, &wv);
-        if (p.weights && valid && h == 0) p.weights[ray * S + s] = wv;
-#if ACN_DIAG_PHASE
-        dg_comp += (uint32_t)__builtin_amdgcn_s_memtime() - (uint32_t)dB;
-#endif
-        const int stop = __builtin_amdgcn_readfirstlane((int)(acc.T < (double)p.tau));
-        if (stop) { s0 += 32; break; }
+    return RayIn{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], rp[6], rp[7], p.jitter ? p.jitter + ray * p.S : nullptr};
+}
+
+// t of sample sc (stratified_t_vals): the linspace value for eval rays, the jittered one otherwise.  Every render
+// kernel takes its sample positions from these two, so the kernels stay bit-equal to each other.
+__device__ __forceinline__ float sample_t(float near, float far, int sc, int S, float step, const float* jit) {
+    if (!jit) {
+        const int i0 = sc < S - 1 ? sc : S - 2;
+        const float ta = tlin_sel(near, far, i0, S, step), tb = tlin_sel(near, far, i0 + 1, S, step);
+        return sc < S - 1 ? ta : tb;
     }
-    SL_MARK(ray, 4)
-    if (p.weights && h == 0)  // samples skipped by early termination carry zero weight
-        for (int s = s0 + j; s < S; s += 32) p.weights[ray * S + s] = 0.0f;
+    return tval(near, far, sc, S, jit);
+}
+// ... and dist = t[i+1] - t[i], the last one repeated (ray_rendering.py:144-145)
+__device__ __forceinline__ float sample_t_dist(float near, float far, int sc, int S, float step, const float* jit,
+                                               float& dist) {
+    if (!jit) {
+        const int i0 = sc < S - 1 ? sc : S - 2;
+        const float ta = tlin_sel(near, far, i0, S, step), tb = tlin_sel(near, far, i0 + 1, S, step);
+        dist = tb - ta;
+        return sc < S - 1 ? ta : tb;
+    }
+    const float t = tval(near, far, sc, S, jit);
+    const float tn = (sc < S - 1) ? tval(near, far, sc + 1, S, jit) : t;
+    const float tp = (sc == S - 1 && S > 1) ? tval(near, far, sc - 1, S, jit) : t;
+    dist = (sc < S - 1) ? (tn - t) : (t - tp);
+    return t;
+}
+
+// The end of a ray: background, the double reductions of the per-lane partials, the background blend, the outputs
+__device__ __forceinline__ void finish_and_store(const RayAcc& acc, const BgArgs& bg, float dx, float dy, float dz,
+                                                 int lane, int64_t ray, const RenderParams& p) {
     float bgc[3];
     background(bg, dx, dy, dz, lane, bgc);
     float r, g, b, dd, a;
@@ -1064,30 +929,75 @@ __device__ __forceinline__ void render_ray(const RenderParams& p, const BgArgs& 
         p.rgb[ray * 3 + 2] = b;
         p.depth[ray] = dd;
         p.acc[ray] = a;
-#if ACN_DIAG_CLOCK
-        p.depth[ray] = (float)(__builtin_amdgcn_s_memtime() - diag_t0) * 100.0f /
-                       (float)(__builtin_amdgcn_s_memrealtime() - diag_r0);
-#endif
-#if ACN_DIAG_WAVETIME
-        p.rgb[ray * 3 + 0] = __int_as_float((int)diag_w0);
-        p.rgb[ray * 3 + 1] = __int_as_float((int)(uint32_t)__builtin_amdgcn_s_memrealtime());
-        p.rgb[ray * 3 + 2] = __int_as_float((int)((__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xffffu) |
-                                                   (__builtin_amdgcn_s_getreg((31 << 11) | 20) << 16)));
-#endif
-#if ACN_DIAG_PHASE  // cycles per tile: depth <- hash phase, acc <- MLP phase, rgb.r <- compositing
-        p.depth[ray] = (float)dg_hash / (float)dg_n;
-        p.acc[ray] = (float)dg_mlp / (float)dg_n;
-        p.rgb[ray * 3] = (float)dg_comp / (float)dg_n;
-#endif
     }
+}
+
+// XCD bands: workgroups are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8), so when the grid is a
+// multiple of 8, XCD x walks the x-th contiguous eighth of the n items (rays in visiting order).  With a spatially
+// coherent order (ray_order_kernel, or pixel-ordered full frames) each XCD's 4 MB L2 then serves the hash cells of
+// one image region instead of the whole frame.  per = items a workgroup takes at a time; the workgroup walks
+// first, first + stride, ... below hi.
+__device__ __forceinline__ void xcd_band(int64_t n, int64_t per, int64_t& first, int64_t& hi, int64_t& stride) {
+    if ((gridDim.x & 7) == 0) {
+        const int64_t chunk = (n + 7) >> 3;
+        const int64_t lo = min(n, (int64_t)(blockIdx.x & 7) * chunk);
+        hi = min(n, lo + chunk);
+        first = lo + (int64_t)(blockIdx.x >> 3) * per;
+        stride = (int64_t)(gridDim.x >> 3) * per;
+    } else {
+        hi = n;
+        first = (int64_t)blockIdx.x * per;
+        stride = (int64_t)gridDim.x * per;
+    }
+}
+
+// One ray, front to back in 32-sample tiles: t-values -> field(px, py, pz, shv, folded, y...) ->
+// volume_render conditioning -> compositing -> background -> outputs.  `field` evaluates the
+// (routed) container for this lane's sample; it is a template callable so the single-expert, the
+// LDS-resident and the slot-staged kernels share this body.
+template <class FieldFn>
+__device__ __forceinline__ void render_ray(const RenderParams& p, const BgArgs& bg, int64_t ray, int lane, float step,
+                                           FieldFn&& field) {
+    const int j = lane & 31, h = lane >> 5;
+    const int S = p.S;
+    const RayIn r = load_ray(p, ray);
+    float sh[16], shv[8];
+    dir_sh(r.dx, r.dy, r.dz, sh);
+    sh_rows_for_half(sh, h, shv);
+    uint32_t folded = 0u;
+    RayAcc acc{1.0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    int s0 = 0;
+    for (; s0 < S; s0 += 32) {
+        const int s = s0 + j;
+        const bool valid = s < S;
+        const int sc = valid ? s : S - 1;
+        float dist;
+        const float t = sample_t_dist(r.near, r.far, sc, S, step, r.jit, dist);
+        const float px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;
+        float yr, yg, yb, ys;
+        field(sc, px, py, pz, shv, folded, yr, yg, yb, ys);
+        // volume_render input conditioning (:140-143)
+        yr = clamp_nan(yr, 0.0f, 1.0f);
+        yg = clamp_nan(yg, 0.0f, 1.0f);
+        yb = clamp_nan(yb, 0.0f, 1.0f);
+        float sig = clamp_min_nan(ys, 0.0f);
+        if (p.sigma_scale != 1.0f) sig = sig * p.sigma_scale;
+        float wv;
+        composite_tile(acc, valid, yr, yg, yb, sig, t, dist, j, &wv);
+        if (p.weights && valid && h == 0) p.weights[ray * S + s] = wv;
+        const int stop = __builtin_amdgcn_readfirstlane((int)(acc.T < (double)p.tau));
+        if (stop) { s0 += 32; break; }
+    }
+    if (p.weights && h == 0)  // samples skipped by early termination carry zero weight
+        for (int s = s0 + j; s < S; s += 32) p.weights[ray * S + s] = 0.0f;
+    finish_and_store(acc, bg, r.dx, r.dy, r.dz, lane, ray, p);
 }
 
 template <int INTERP, int KL, int ROUTE>
 __global__ void __launch_bounds__(1024, 4) render_kernel(FieldCfg cfg, BgArgs bg, RenderParams p) {
-    constexpr bool FOLD = ACN_SHFOLD != 0;
     constexpr int KF = ROUTE == 0 ? 1 : (KL == 2 ? 2 : kMaxK);  // experts a ray may fold
     __shared__ __attribute__((aligned(16))) float smem[(KL > 0 ? KL : 1) * PK_FLOATS];
-    __shared__ __attribute__((aligned(16))) float cbuf[FOLD ? 16 * KF * 64 : 4];
+    __shared__ __attribute__((aligned(16))) float cbuf[16 * KF * 64];
     const float* W = p.packed;
     if (KL > 0) {
         stage_weights<KL>(smem, p.packed);
@@ -1095,31 +1005,16 @@ __global__ void __launch_bounds__(1024, 4) render_kernel(FieldCfg cfg, BgArgs bg
     }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // provably uniform: ray data in SGPRs
-    float* cb = FOLD ? cbuf + wave * KF * 64 : nullptr;
+    float* cb = cbuf + wave * KF * 64;
     const float step = 1.0f / (float)(p.S - 1);
-    // XCD bands: workgroups are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8), so
-    // when the grid is a multiple of 8, XCD x walks the x-th contiguous eighth of the visiting order.
-    // With a spatially coherent order (ray_order_kernel, or pixel-ordered full frames) each XCD's
-    // 4 MB L2 then serves the hash cells of one image region instead of the whole frame.
-    const int64_t wpb = blockDim.x >> 6;
-    int64_t pos, hi, stride;
-    if ((gridDim.x & 7) == 0) {
-        const int64_t chunk = (p.N + 7) >> 3;
-        const int64_t lo = min(p.N, (int64_t)(blockIdx.x & 7) * chunk);
-        hi = min(p.N, lo + chunk);
-        pos = lo + (int64_t)(blockIdx.x >> 3) * wpb + wave;
-        stride = (int64_t)(gridDim.x >> 3) * wpb;
-    } else {
-        hi = p.N;
-        pos = (int64_t)blockIdx.x * wpb + wave;
-        stride = (int64_t)gridDim.x * wpb;
-    }
-    for (; pos < hi; pos += stride) {
+    int64_t pos, hi, stride;   // one ray per wave: the workgroup takes blockDim.x / 64 positions at a time
+    xcd_band(p.N, blockDim.x >> 6, pos, hi, stride);
+    for (pos += wave; pos < hi; pos += stride) {
         const int64_t ray = p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[pos]) : pos;
         render_ray(p, bg, ray, lane, step,
                    [&](int, float px, float py, float pz, const float (&shv)[8], uint32_t& folded, float& yr, float& yg,
                        float& yb, float& ys) {
-                       container_tile<INTERP, ROUTE, FOLD>(cfg, W, px, py, pz, shv, cb, &folded, lane, yr, yg, yb, ys);
+                       container_tile<INTERP, ROUTE, true>(cfg, W, px, py, pz, shv, cb, &folded, lane, yr, yg, yb, ys);
                    });
     }
 }
@@ -1127,32 +1022,20 @@ __global__ void __launch_bounds__(1024, 4) render_kernel(FieldCfg cfg, BgArgs bg
 // ------------------------------------------------------------------------------------------
 // Single-expert render with the workgroup's field tiles shared (render_ws_kernel, the C2 path when there is no
 // early termination).  render_kernel gives every wave one ray, and all 4096 waves of a C2 batch are resident
-// at once, so a CU runs until its slowest ray ends: the per-wave timeline (tools/micro/wave_times.py) shows rays
-// of 190-295 us in a 297 us launch, 12 of 16 waves resident on average.  Here the 16 rays of a round are
-// split into their 32-sample tiles (the field's MFMA unit), and the waves take tiles from an LDS counter
-// (tile-major, so wave w starts on ray w's first tile, as before).  A tile's field values (rgb, sigma per
-// sample) go to LDS; the wave whose tile completes a ray composites that ray from LDS with render_ray's exact
-// sequence (t, dist, conditioning, composite_tile in tile order, background, reductions), so every output is
+// at once, so a CU runs until its slowest ray ends: a per-wave timeline showed rays of 190-295 us in a 297 us
+// launch, 12 of 16 waves resident on average.  Here the 16 rays of a round are split into 32-sample tiles (the
+// field's MFMA unit; depth tiles, below), and the waves take tiles from an LDS counter.  A tile's field values
+// (rgb, sigma per sample) go to LDS; after a barrier wave w composites the round's ray w from LDS with render_ray's
+// exact sequence (t, dist, conditioning, composite_tile in tile order, background, reductions), so every output is
 // bit-identical to render_kernel.  Early ray termination needs the tiles in order: tau > 0 keeps render_kernel.
-#ifndef ACN_RENDER_WS
-#define ACN_RENDER_WS 1
-#endif
 constexpr int kWsMaxS = 256;   // LDS field buffer: 16 rays x kWsMaxS samples x 16 B = 64 KB
-#ifndef ACN_WS_CHECK
-#define ACN_WS_CHECK 0   // diagnostic self-check build (tools/dbg/selfcheck.py)
-#endif
-#ifndef ACN_WS_PREFOLD
-#define ACN_WS_PREFOLD 1  // fold each round ray's SH colour bias once, at the round start (not per tile)
-#endif
-#ifndef ACN_WS_DTILE
-// R > 0: depth tiles -- a field tile = R of the round's 16 rays at 32 / R consecutive samples, instead of one ray's
-// 32 consecutive samples (0).  A wave's gathers then come from neighbouring rays at nearby depths, whose points
-// share hash lines at more levels than one ray's consecutive samples do.  C2: 3.72e9 (0) -> 3.79 (16) / 3.89 (8) /
-// 3.90 (4) / 3.86e9 (2) ray-samples/s (profiles/r06y_ws_dtile_ab.jsonl); outputs bit-identical (the field of a
-// sample does not depend on its tile-mates; compositing reads LDS per ray as before).  The self-check build
-// (ACN_WS_CHECK) keeps ray tiles.
-#define ACN_WS_DTILE (ACN_WS_CHECK ? 0 : 8)
-#endif
+// Depth tiles -- a field tile = kWsDtile of the round's 16 rays at 32 / kWsDtile consecutive samples, instead of one
+// ray's 32 consecutive samples (ray tiles).  A wave's gathers then come from neighbouring rays at nearby depths, whose
+// points share hash lines at more levels than one ray's consecutive samples do.  C2: 3.72e9 (ray tiles) -> 3.79 (16) /
+// 3.89 (8) / 3.90 (4) / 3.86e9 (2) ray-samples/s (profiles/r06y_ws_dtile_ab.jsonl); outputs bit-identical (the field
+// of a sample does not depend on its tile-mates; compositing reads LDS per ray as before).
+constexpr int kWsDtile = 8;
+static_assert(16 % kWsDtile == 0, "kWsDtile: rays per tile divide 16");
 
 // composite one ray from its samples' field values in LDS (ys[s] = rgb, sigma of sample s, as the field tile
 // returned them): render_ray's exact sequence without early termination -- t and dist, the volume_render
@@ -1161,27 +1044,14 @@ __device__ __forceinline__ void composite_ray_lds(const RenderParams& p, const B
                                                   const f32x4* __restrict__ ys, int lane, float step) {
     const int j = lane & 31, h = lane >> 5;
     const int S = p.S;
-    const float* rq = p.rays + ray * 8;
-    const float dx = rq[3], dy = rq[4], dz = rq[5];
-    const float near = rq[6], far = rq[7];
-    const float* jit = p.jitter ? p.jitter + ray * S : nullptr;
+    const RayIn r = load_ray(p, ray);   // the origin is not used here
     RayAcc acc{1.0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     for (int s0 = 0; s0 < S; s0 += 32) {
         const int s = s0 + j;
         const bool valid = s < S;
         const int sc = valid ? s : S - 1;
-        float t, dist;
-        if (!jit) {
-            const int i0 = sc < S - 1 ? sc : S - 2;
-            const float ta = tlin_sel(near, far, i0, S, step), tb = tlin_sel(near, far, i0 + 1, S, step);
-            t = sc < S - 1 ? ta : tb;
-            dist = tb - ta;
-        } else {
-            t = tval(near, far, sc, S, jit);
-            const float tn = (sc < S - 1) ? tval(near, far, sc + 1, S, jit) : t;
-            const float tp = (sc == S - 1 && S > 1) ? tval(near, far, sc - 1, S, jit) : t;
-            dist = (sc < S - 1) ? (tn - t) : (t - tp);
-        }
+        float dist;
+        const float t = sample_t_dist(r.near, r.far, sc, S, step, r.jit, dist);
         const f32x4 y = ys[sc];
         const float cr = clamp_nan(y[0], 0.0f, 1.0f);
         const float cg = clamp_nan(y[1], 0.0f, 1.0f);
@@ -1192,53 +1062,23 @@ __device__ __forceinline__ void composite_ray_lds(const RenderParams& p, const B
         composite_tile(acc, valid, cr, cg, cbl, sig, t, dist, j, &wv);
         if (p.weights && valid && h == 0) p.weights[ray * S + s] = wv;
     }
-    float bgc[3];
-    background(bg, dx, dy, dz, lane, bgc);
-    float r, g, b, dd, a;
-    finish_ray(acc, r, g, b, dd, a);
-    if (lane == 0) {
-        if (bg.mode != ACN_BG_NONE) {
-            const float om = 1.0f - a;
-            r = r + om * bgc[0];
-            g = g + om * bgc[1];
-            b = b + om * bgc[2];
-        }
-        p.rgb[ray * 3 + 0] = r;
-        p.rgb[ray * 3 + 1] = g;
-        p.rgb[ray * 3 + 2] = b;
-        p.depth[ray] = dd;
-        p.acc[ray] = a;
-    }
+    finish_and_store(acc, bg, r.dx, r.dy, r.dz, lane, ray, p);
 }
 
 template <int INTERP>
 __global__ void __launch_bounds__(1024, 4) render_ws_kernel(FieldCfg cfg, BgArgs bg, RenderParams p) {
-    constexpr bool FOLD = ACN_SHFOLD != 0;
     __shared__ __attribute__((aligned(16))) float smem[PK_FLOATS];
-    __shared__ __attribute__((aligned(16))) float cbuf[FOLD ? 16 * 64 : 4];
+    __shared__ __attribute__((aligned(16))) float cbuf[16 * 64];   // the round rays' folded colour biases
     __shared__ __attribute__((aligned(16))) f32x4 ybuf[16 * kWsMaxS];
     __shared__ int qhead;
-    __shared__ int done[16];
     stage_weights<1>(smem, p.packed);
     const float* W = smem;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* cb = FOLD ? cbuf + wave * 64 : nullptr;
     const int S = p.S;
-    const int T = (S + 31) >> 5;
     const float step = 1.0f / (float)(S - 1);
     // the rays of a round: 16 consecutive positions, XCD bands as in render_kernel
     int64_t base, hi, stride;
-    if ((gridDim.x & 7) == 0) {
-        const int64_t chunk = (p.N + 7) >> 3;
-        const int64_t lo = min(p.N, (int64_t)(blockIdx.x & 7) * chunk);
-        hi = min(p.N, lo + chunk);
-        base = lo + (int64_t)(blockIdx.x >> 3) * 16;
-        stride = (int64_t)(gridDim.x >> 3) * 16;
-    } else {
-        hi = p.N;
-        base = (int64_t)blockIdx.x * 16;
-        stride = (int64_t)gridDim.x * 16;
-    }
+    xcd_band(p.N, 16, base, hi, stride);
     for (; base < hi; base += stride) {   // block-uniform
         // the lane index re-derived per round through an opaque copy: the per-lane LDS addresses and constants
         // formed from it stay inside the loop instead of being hoisted into registers held across it (spilled)
@@ -1247,9 +1087,7 @@ __global__ void __launch_bounds__(1024, 4) render_ws_kernel(FieldCfg cfg, BgArgs
         const float kz = __int_as_float(opaque_s(0));   // +0.0f for the SH coefficients (acn_device.h)
         const int nr = (int)min((int64_t)16, hi - base);
         if (tid == 0) qhead = 0;
-        if (tid < 16) done[tid] = 0;
-        constexpr bool PRE = FOLD && ACN_WS_PREFOLD;
-        if (PRE && wave < nr) {
+        if (wave < nr) {
             // wave w folds round slot w's colour bias into cbuf[w] once; every tile of that ray reads it there
             const int64_t r0 = p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[base + wave]) : base + wave;
             const float* rp = p.rays + r0 * 8;
@@ -1259,132 +1097,46 @@ __global__ void __launch_bounds__(1024, 4) render_ws_kernel(FieldCfg cfg, BgArgs
             fold_sh_bias(W, sv, lane, cbuf + wave * 64);
         }
         __syncthreads();
-#if ACN_WS_DTILE
-        static_assert(!ACN_WS_DTILE || (FOLD && ACN_WS_PREFOLD && !ACN_WS_CHECK), "depth tiles read the pre-folded bias");
-        static_assert(16 % (ACN_WS_DTILE > 0 ? ACN_WS_DTILE : 1) == 0, "ACN_WS_DTILE: rays per tile divide 16");
-        {
-            // tile = R rays of one group of the round at D = 32 / R consecutive samples; lane j: slot g R + j % R,
-            // sample q D + j / R (both halves of the tile: the same sample).  Slots past the round's rays repeat
-            // its last ray and write nothing.
-            constexpr int R = ACN_WS_DTILE, D = 32 / R, NG = 16 / R;
-            const int ND = (S + D - 1) / D;
-            const float shz[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            int gcur = -1;
-            int slot = 0;
-            float ox = 0.0f, oy = 0.0f, oz = 0.0f, dx = 0.0f, dy = 0.0f, dz = 0.0f, near = 0.0f, far = 0.0f;
-            const float* jit = nullptr;
-            for (;;) {
-                int item = 0;
-                if (lane == 0) item = __hip_atomic_fetch_add(&qhead, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                item = __builtin_amdgcn_readlane(item, 0);
-                if (item >= NG * ND) break;
-                const int g = NG == 1 ? 0 : item % NG, q = NG == 1 ? item : item / NG;
-                if (g != gcur) {   // wave-uniform
-                    slot = g * R + (j % R);
-                    const int ls = slot < nr ? slot : nr - 1;
-                    const int64_t ray = p.order ? (int64_t)p.order[base + ls] : base + ls;
-                    const float* rp = p.rays + ray * 8;
-                    ox = rp[0], oy = rp[1], oz = rp[2], dx = rp[3], dy = rp[4], dz = rp[5];
-                    near = rp[6], far = rp[7];
-                    jit = p.jitter ? p.jitter + ray * S : nullptr;
-                    gcur = g;
-                }
-                const int s = q * D + j / R;
-                const int sc = s < S ? s : S - 1;
-                float t;
-                if (!jit) {
-                    const int i0 = sc < S - 1 ? sc : S - 2;
-                    const float ta = tlin_sel(near, far, i0, S, step), tb = tlin_sel(near, far, i0 + 1, S, step);
-                    t = sc < S - 1 ? ta : tb;
-                } else {
-                    t = tval(near, far, sc, S, jit);
-                }
-                const float px = ox + dx * t, py = oy + dy * t, pz = oz + dz * t;
-                uint32_t fl = 1u;
-                float yr, yg, yb, ys;
-                container_tile<INTERP, 0, FOLD>(cfg, W, px, py, pz, shz, cbuf + slot * 64, &fl, lane, yr, yg, yb, ys);
-                if (h == 0 && s < S && slot < nr) {
-                    f32x4 v;
-                    v[0] = yr, v[1] = yg, v[2] = yb, v[3] = ys;
-                    ybuf[slot * kWsMaxS + s] = v;
-                }
-            }
-            __syncthreads();   // every sample of the round's rays is in ybuf
-            if (wave < nr) {
-                const int64_t ray_w = p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[base + wave]) : base + wave;
-                composite_ray_lds(p, bg, ray_w, ybuf + wave * kWsMaxS, lane, step);
-            }
-            __syncthreads();
-            continue;
-        }
-#endif
-        int64_t cur = -1;
-        uint32_t folded = 0u;
-        float shv[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        float ox = 0.0f, oy = 0.0f, oz = 0.0f, dx = 0.0f, dy = 0.0f, dz = 0.0f, near = 0.0f, far = 0.0f;
-        const float* jit = nullptr;
+        // tile = R rays of one group of the round at D = 32 / R consecutive samples; lane j: slot g R + j % R,
+        // sample q D + j / R (both halves of the tile: the same sample).  Slots past the round's rays repeat
+        // its last ray and write nothing.
+        constexpr int R = kWsDtile, D = 32 / R, NG = 16 / R;
+        const int ND = (S + D - 1) / D;
+        const float shz[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        int gcur = -1;
+        int slot = 0;
+        RayIn r{};
         for (;;) {
             int item = 0;
             if (lane == 0) item = __hip_atomic_fetch_add(&qhead, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             item = __builtin_amdgcn_readlane(item, 0);
-            if (item >= nr * T) break;
-            const int tile = item / nr, slot = item - tile * nr;
-            const int64_t ray = p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[base + slot]) : base + slot;
-            if (ray != cur) {
-                const float* rp = p.rays + ray * 8;
-                ox = rp[0], oy = rp[1], oz = rp[2], dx = rp[3], dy = rp[4], dz = rp[5];
-                near = rp[6], far = rp[7];
-                jit = p.jitter ? p.jitter + ray * S : nullptr;
-                if (!PRE || ACN_WS_CHECK) {
-                    float sh[16];
-                    dir_sh(dx, dy, dz, sh, kz);
-                    sh_rows_for_half(sh, h, shv);
-                    if (!PRE) folded = 0u;
-                }
-                cur = ray;
+            if (item >= NG * ND) break;
+            const int g = NG == 1 ? 0 : item % NG, q = NG == 1 ? item : item / NG;
+            if (g != gcur) {   // wave-uniform
+                slot = g * R + (j % R);
+                const int ls = slot < nr ? slot : nr - 1;
+                r = load_ray(p, p.order ? (int64_t)p.order[base + ls] : base + ls);
+                gcur = g;
             }
-            if (PRE) {   // the slot's pre-folded bias (shv is not read by a folded field tile)
-                cb = cbuf + slot * 64;
-                folded = 1u;
-            }
-            const int s = tile * 32 + j;
+            const int s = q * D + j / R;
             const int sc = s < S ? s : S - 1;
-            float t;
-            if (!jit) {
-                const int i0 = sc < S - 1 ? sc : S - 2;
-                const float ta = tlin_sel(near, far, i0, S, step), tb = tlin_sel(near, far, i0 + 1, S, step);
-                t = sc < S - 1 ? ta : tb;
-            } else {
-                t = tval(near, far, sc, S, jit);
-            }
-            const float px = ox + dx * t, py = oy + dy * t, pz = oz + dz * t;
+            const float t = sample_t(r.near, r.far, sc, S, step, r.jit);
+            const float px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;
+            uint32_t fl = 1u;
             float yr, yg, yb, ys;
-            container_tile<INTERP, 0, FOLD>(cfg, W, px, py, pz, shv, cb, &folded, lane, yr, yg, yb, ys);
-#if ACN_WS_CHECK  // diagnostic build only: the tile evaluated twice; a differing lane poisons its sample (NaN rgb).
-            {   // The second evaluation runs colour layer 0 unfolded, SH k-step first: bit for bit the fold + folded
-                // layer (field_tile), so a stale operand in the per-ray fold is caught as well
-                float cr, cg, cbb, cs;
-                field_tile<INTERP, false, true>(W, cfg.ex[0], cfg.log2T, px, py, pz, shv, nullptr, lane, cr, cg, cbb, cs);
-                cs = trunc_exp(cs);
-                if (__float_as_uint(cr) != __float_as_uint(yr) || __float_as_uint(cg) != __float_as_uint(yg) ||
-                    __float_as_uint(cbb) != __float_as_uint(yb) || __float_as_uint(cs) != __float_as_uint(ys))
-                    yr = __int_as_float(0x7fc00000);
-            }
-#endif
-            if (h == 0 && s < S) {
+            container_tile<INTERP, 0, true>(cfg, W, px, py, pz, shz, cbuf + slot * 64, &fl, lane, yr, yg, yb, ys);
+            if (h == 0 && s < S && slot < nr) {
                 f32x4 v;
                 v[0] = yr, v[1] = yg, v[2] = yb, v[3] = ys;
                 ybuf[slot * kWsMaxS + s] = v;
             }
-            // the wave's LDS writes are ordered before its count (workgroup-scope release / acquire)
-            int old = 0;
-            if (lane == 0) old = __hip_atomic_fetch_add(&done[slot], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-            old = __builtin_amdgcn_readlane(old, 0);
-            if (old != T - 1) continue;
-            // this tile completed the ray: composite it (render_ray's sequence, no early termination)
-            composite_ray_lds(p, bg, ray, ybuf + slot * kWsMaxS, lane, step);
         }
-        __syncthreads();   // ybuf / qhead / done reused by the next round
+        __syncthreads();   // every sample of the round's rays is in ybuf
+        if (wave < nr) {
+            const int64_t ray_w = p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[base + wave]) : base + wave;
+            composite_ray_lds(p, bg, ray_w, ybuf + wave * kWsMaxS, lane, step);
+        }
+        __syncthreads();   // ybuf / qhead reused by the next round
     }
 }
 
@@ -1395,9 +1147,6 @@ __global__ void __launch_bounds__(1024, 4) render_ws_kernel(FieldCfg cfg, BgArgs
 // with rays sorted by owning expert, parallel.expert_sorted_plan, a workgroup's rays mostly need
 // the same one or two experts, so staging is rare).  A sample whose expert is not resident is
 // evaluated from the packed image in global memory (L2), without the SH fold.
-#ifndef ACN_SLOTS_SINGLE
-#define ACN_SLOTS_SINGLE 1  // single-expert rays (kSingleRay) skip the per-sample routing and blend
-#endif
 // Bit kSingleRay of the returned mask: every sample of the ray is routed to ONE expert with weight
 // exactly 1.0f (soft: (1/d)/den with den = 1/d; hard: always), so the container's blend
 // 0 + y_k * 1.0f is y_k bit for bit and the ray can skip the per-sample routing and blend.
@@ -1442,13 +1191,10 @@ __device__ __forceinline__ uint32_t ray_expert_mask(const FieldCfg& cfg, int rou
     uint32_t m = 0u;
     bool exact = true;
     if (live) {
-        const float* rp = p.rays + ray * 8;
-        const float ox = rp[0], oy = rp[1], oz = rp[2], dx = rp[3], dy = rp[4], dz = rp[5];
-        const float near = rp[6], far = rp[7];
-        const float* jit = p.jitter ? p.jitter + ray * p.S : nullptr;
+        const RayIn r = load_ray(p, ray);
         for (int s = lane; s < p.S; s += 64) {
-            const float t = jit ? tval(near, far, s, p.S, jit) : tlin_sel(near, far, s, p.S, step);
-            const float px = ox + dx * t, py = oy + dy * t, pz = oz + dz * t;
+            const float t = r.jit ? tval(r.near, r.far, s, p.S, r.jit) : tlin_sel(r.near, r.far, s, p.S, step);
+            const float px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;
             if (route == 1) {
                 soft_route_bits(cfg, px, py, pz, m, exact);
             } else {
@@ -1459,16 +1205,10 @@ __device__ __forceinline__ uint32_t ray_expert_mask(const FieldCfg& cfg, int rou
     uint32_t any = 0u;  // OR over the wave: one ballot per expert (scalar), no LDS round trips
     for (int k = 0; k < cfg.K; ++k)
         if (__ballot((m >> k) & 1u) != 0ull) any |= 1u << k;
-    if (ACN_SLOTS_SINGLE && __builtin_popcount(any) == 1 && __ballot(!exact) == 0ull) any |= kSingleRay;
+    if (__builtin_popcount(any) == 1 && __ballot(!exact) == 0ull) any |= kSingleRay;
     return any;
 }
 
-#ifndef ACN_ORDER_DIAG
-#define ACN_ORDER_DIAG 0  // diagnostic builds of ray_order_kernel (1-3: stop after a phase; wrong orders)
-#endif
-#ifndef ACN_SLOTS_BAND
-#define ACN_SLOTS_BAND 0
-#endif
 #ifndef ACN_SLOTS_CHECK
 #define ACN_SLOTS_CHECK 0   // diagnostic self-check build (tools/dbg/selfcheck.py; 2: mismatches recorded)
 #endif
@@ -1488,166 +1228,144 @@ __device__ __forceinline__ bool cbg_holds(uint32_t folded, int k) {
 __device__ __forceinline__ uint32_t cbg_set(uint32_t folded, int k) {
     return (folded & 7u) | 8u | ((uint32_t)k << 4);
 }
+// The two LDS expert slots of a workgroup round (render_slots_kernel, render_wss_kernel): the two most needed
+// experts by the round's counts cq[k] (the same choice in every wave: same counts, same slot state), an expert
+// kept in the slot it already occupies, and the slots that change restaged from the packed images (with a barrier).
+// sk0 / sk1: the slots' experts, wave-uniform registers updated identically by every wave.
+__device__ __forceinline__ void choose_slots(const int* cq, int K, const float* __restrict__ packed, float* smem,
+                                             int tid, int& sk0, int& sk1) {
+    int b0 = -1, b1 = -1;
+    for (int k = 0; k < K; ++k) {
+        const int c = cq[k];
+        if (c == 0) continue;
+        if (b0 < 0 || c > cq[b0]) { b1 = b0; b0 = k; }
+        else if (b1 < 0 || c > cq[b1]) b1 = k;
+    }
+    b0 = __builtin_amdgcn_readfirstlane(b0);
+    b1 = __builtin_amdgcn_readfirstlane(b1);
+    if (b0 == sk1 || b1 == sk0) { const int t = b0; b0 = b1; b1 = t; }
+    const bool rs0 = b0 >= 0 && b0 != sk0, rs1 = b1 >= 0 && b1 != sk1;
+    if (b0 >= 0) sk0 = b0;
+    if (b1 >= 0) sk1 = b1;
+    if (rs0 || rs1) {   // block-uniform
+        for (int sl = 0; sl < 2; ++sl) {
+            if (sl == 0 ? !rs0 : !rs1) continue;
+            const f32x4* src = reinterpret_cast<const f32x4*>(packed + (size_t)(sl == 0 ? sk0 : sk1) * PK_FLOATS);
+            f32x4* dst = reinterpret_cast<f32x4*>(smem + sl * PK_FLOATS);
+            for (int i = tid; i < PK_FLOATS / 4; i += blockDim.x) dst[i] = src[i];
+        }
+        __syncthreads();
+    }
+}
+
 // the field of one 32-sample tile in render_slots_kernel: LDS slot experts, the rest from the packed images
 // in global memory (folded colour bias in cb[slot] / cbg); single = one expert with weight 1.0f on every sample
-template <int INTERP, int ROUTE, bool FOLD>
+template <int INTERP, int ROUTE>
 __device__ __forceinline__ void slots_field(const FieldCfg& cfg, const RenderParams& p, const float* smem, float* cb,
                                             float* cbg, int k0, int k1, bool single, int k_single, float px, float py,
                                             float pz, const float (&shv)[8], uint32_t& folded, int lane, float& yr,
                                             float& yg, float& yb, float& ys) {
-        if (single) {  // wave-uniform: one expert, weight 1.0f on every sample
-            const int k = k_single;
-            const int sl = (k == k0) ? 0 : ((k == k1) ? 1 : -1);
-            float sg;
-            if (sl >= 0) {
-                const float* Wk = smem + sl * PK_FLOATS;
-                float* cbk = FOLD ? cb + sl * 64 : nullptr;
-                if (FOLD && !((folded >> sl) & 1u)) {
-                    fold_sh_bias(Wk, shv, lane, cbk);
-                    folded |= 1u << sl;
-                }
-                field_tile<INTERP, FOLD, false, ACN_FIELD_CHECK != 0>(Wk, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbk, lane, yr,
-                                         yg, yb, sg);
-            } else {
-                const float* Wg = p.packed + (size_t)k * PK_FLOATS;
-                if (FOLD && !cbg_holds(folded, k)) {
-                    fold_sh_bias(Wg, shv, lane, cbg);
-                    folded = cbg_set(folded, k);
-                }
-                field_tile<INTERP, FOLD, false, ACN_FIELD_CHECK != 0>(Wg, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbg, lane, yr,
-                                         yg, yb, sg);
+    constexpr bool FCHK = ACN_FIELD_CHECK != 0;
+    if (single) {  // wave-uniform: one expert, weight 1.0f on every sample
+        const int k = k_single;
+        const int sl = (k == k0) ? 0 : ((k == k1) ? 1 : -1);
+        float sg;
+        if (sl >= 0) {
+            const float* Wk = smem + sl * PK_FLOATS;
+            float* cbk = cb + sl * 64;
+            if (!((folded >> sl) & 1u)) {
+                fold_sh_bias(Wk, shv, lane, cbk);
+                folded |= 1u << sl;
             }
-            ys = trunc_exp(sg);
-            return;
+            field_tile<INTERP, true, false, FCHK>(Wk, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbk, lane, yr, yg, yb, sg);
+        } else {
+            const float* Wg = p.packed + (size_t)k * PK_FLOATS;
+            if (!cbg_holds(folded, k)) {
+                fold_sh_bias(Wg, shv, lane, cbg);
+                folded = cbg_set(folded, k);
+            }
+            field_tile<INTERP, true, false, FCHK>(Wg, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbg, lane, yr, yg, yb, sg);
         }
-    #if ACN_DIAG_SLOTS_NOMULTI  // diagnostic build only: the multi-expert blend path removed (register study)
-        yr = yg = yb = ys = 0.0f;
+        ys = trunc_exp(sg);
         return;
-    #endif
-        const RouteState st = route_prep<ROUTE>(cfg, px, py, pz);
-        yr = yg = yb = ys = 0.0f;
-        for (int k = 0; k < cfg.K; ++k) {
-            const float wk = (ROUTE == 1) ? route_weight(cfg, st, k, px, py, pz) : 0.0f;
-            const bool need = (ROUTE == 1) ? (wk > 0.0f) : (st.hard == k);
-            if (__ballot(need) == 0ull) continue;
-            float r, g, b, sg;
-            const int sl = (k == k0) ? 0 : ((k == k1) ? 1 : -1);
-            if (sl >= 0) {
-                const float* Wk = smem + sl * PK_FLOATS;
-                float* cbk = FOLD ? cb + sl * 64 : nullptr;
-                if (FOLD && !((folded >> sl) & 1u)) {
-                    fold_sh_bias(Wk, shv, lane, cbk);
-                    folded |= 1u << sl;
-                }
-                field_tile<INTERP, FOLD, false, ACN_FIELD_CHECK != 0>(Wk, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbk, lane, r, g,
-                                         b, sg);
-            } else {
-    #if ACN_SLOTS_NOFALLBACK  // diagnostic only: non-resident experts skipped
-                r = g = b = sg = 0.0f;
-    #else
-                const float* Wg = p.packed + (size_t)k * PK_FLOATS;
-                if (FOLD && !cbg_holds(folded, k)) {
-                    fold_sh_bias(Wg, shv, lane, cbg);
-                    folded = cbg_set(folded, k);
-                }
-                field_tile<INTERP, FOLD, false, ACN_FIELD_CHECK != 0>(Wg, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbg, lane, r, g,
-                                         b, sg);
-    #endif
+    }
+    const RouteState st = route_prep<ROUTE>(cfg, px, py, pz);
+    yr = yg = yb = ys = 0.0f;
+    for (int k = 0; k < cfg.K; ++k) {
+        const float wk = (ROUTE == 1) ? route_weight(cfg, st, k, px, py, pz) : 0.0f;
+        const bool need = (ROUTE == 1) ? (wk > 0.0f) : (st.hard == k);
+        if (__ballot(need) == 0ull) continue;
+        float r, g, b, sg;
+        const int sl = (k == k0) ? 0 : ((k == k1) ? 1 : -1);
+        if (sl >= 0) {
+            const float* Wk = smem + sl * PK_FLOATS;
+            float* cbk = cb + sl * 64;
+            if (!((folded >> sl) & 1u)) {
+                fold_sh_bias(Wk, shv, lane, cbk);
+                folded |= 1u << sl;
             }
-            sg = trunc_exp(sg);
-            if (need) {
-                if (ROUTE == 1) {
-                    yr = yr + r * wk;
-                    yg = yg + g * wk;
-                    yb = yb + b * wk;
-                    ys = ys + sg * wk;
-                } else {
-                    yr = r; yg = g; yb = b; ys = sg;
-                }
+            field_tile<INTERP, true, false, FCHK>(Wk, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbk, lane, r, g, b, sg);
+        } else {
+            const float* Wg = p.packed + (size_t)k * PK_FLOATS;
+            if (!cbg_holds(folded, k)) {
+                fold_sh_bias(Wg, shv, lane, cbg);
+                folded = cbg_set(folded, k);
+            }
+            field_tile<INTERP, true, false, FCHK>(Wg, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbg, lane, r, g, b, sg);
+        }
+        sg = trunc_exp(sg);
+        if (need) {
+            if (ROUTE == 1) {
+                yr = yr + r * wk;
+                yg = yg + g * wk;
+                yb = yb + b * wk;
+                ys = ys + sg * wk;
+            } else {
+                yr = r; yg = g; yb = b; ys = sg;
             }
         }
+    }
 }
 
 template <int INTERP, int ROUTE>
 __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) render_slots_kernel(FieldCfg cfg, BgArgs bg, RenderParams p) {
-    constexpr bool FOLD = ACN_SHFOLD != 0;
     __shared__ __attribute__((aligned(16))) float smem[2 * PK_FLOATS];
     // per wave: the folded SH bias of the two LDS slots and of the expert read from L2 (every expert's
     // colour layer 0 runs folded, wherever its weights are read from: a ray's arithmetic must not depend on
     // which experts its workgroup round keeps in LDS -- that choice depends on the other rays of the batch)
-    __shared__ __attribute__((aligned(16))) float cbuf[FOLD ? (ACN_SLOTS_THREADS / 64) * 3 * 64 : 4];
+    __shared__ __attribute__((aligned(16))) float cbuf[(ACN_SLOTS_THREADS / 64) * 3 * 64];
     // per-round expert counts, three buffers by round index: round q counts into cnt[q % 3], every wave reads
     // that buffer after the round's barrier, and thread 0 clears cnt[(q + 2) % 3] (read in round q - 1, before
     // this barrier; written again in round q + 2, after the next one) -- one barrier per round, not three
     __shared__ int cnt[3][kMaxK];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* cb = FOLD ? cbuf + wave * 3 * 64 : nullptr;
-    float* cbg = FOLD ? cb + 2 * 64 : nullptr;
+    float* cb = cbuf + wave * 3 * 64;
+    float* cbg = cb + 2 * 64;
     const float step = 1.0f / (float)(p.S - 1);
     if (threadIdx.x < 3 * kMaxK) (&cnt[0][0])[threadIdx.x] = 0;
     __syncthreads();
     // the two LDS slots' experts: wave-uniform registers, updated identically by every wave from the counts
     int sk0 = -1, sk1 = -1, rbuf = 0;
     const int64_t waves_per_wg = blockDim.x >> 6;
-    // XCD bands (as render_kernel): with the grid a multiple of 8, XCD x walks the x-th contiguous
-    // eighth of the rays, so a frame's neighbouring rays share one L2 (ACN_SLOTS_BAND=0: interleaved)
-    int64_t first = (int64_t)blockIdx.x * waves_per_wg, lim = p.norder ? (int64_t)p.norder[0] : p.N,
-            gstride = (int64_t)gridDim.x * waves_per_wg;
-    if (ACN_SLOTS_BAND && (gridDim.x & 7) == 0 && !p.norder) {
-        const int64_t chunk = (((p.N + 7) >> 3) + waves_per_wg - 1) / waves_per_wg * waves_per_wg;
-        const int64_t lo = min(p.N, (int64_t)(blockIdx.x & 7) * chunk);
-        lim = min(p.N, lo + chunk);
-        first = lo + (int64_t)(blockIdx.x >> 3) * waves_per_wg;
-        gstride = (int64_t)(gridDim.x >> 3) * waves_per_wg;
-    }
+    // rounds interleaved over the workgroups (XCD bands as in render_kernel: within +-4% on C4 frames)
+    const int64_t first = (int64_t)blockIdx.x * waves_per_wg, lim = p.norder ? (int64_t)p.norder[0] : p.N,
+                  gstride = (int64_t)gridDim.x * waves_per_wg;
     for (int64_t base = first; base < lim; base += gstride) {
         const bool live = base + wave < lim;
         const int64_t ray = !live ? 0 : (p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[base + wave])
                                                  : base + wave);
-        if (live) { SL_MARK(ray, 0) }
         const uint32_t m = ray_expert_mask(cfg, ROUTE, p, ray, live, step, lane);
-        if (live) { SL_MARK(ray, 1) }
         int* cq = cnt[rbuf];
         if (lane == 0)
             for (int k = 0; k < cfg.K; ++k)
                 if ((m >> k) & 1u) atomicAdd(&cq[k], 1);
         __syncthreads();   // this round's counts complete; every wave is done with the previous round's slots
-        {
-            // the two most needed experts (the same choice in every wave: same counts, same slot state)
-            int b0 = -1, b1 = -1;
-            for (int k = 0; k < cfg.K; ++k) {
-                const int c = cq[k];
-                if (c == 0) continue;
-                if (b0 < 0 || c > cq[b0]) { b1 = b0; b0 = k; }
-                else if (b1 < 0 || c > cq[b1]) b1 = k;
-            }
-            b0 = __builtin_amdgcn_readfirstlane(b0);
-            b1 = __builtin_amdgcn_readfirstlane(b1);
-            const int rclear = rbuf == 0 ? 2 : rbuf - 1;   // (q + 2) % 3
-            if (threadIdx.x < kMaxK) cnt[rclear][threadIdx.x] = 0;
-            rbuf = rbuf == 2 ? 0 : rbuf + 1;
-            // keep an expert in the slot it already occupies
-            if (b0 == sk1 || b1 == sk0) { const int t = b0; b0 = b1; b1 = t; }
-            const bool rs0 = b0 >= 0 && b0 != sk0, rs1 = b1 >= 0 && b1 != sk1;
-            if (b0 >= 0) sk0 = b0;
-            if (b1 >= 0) sk1 = b1;
-            if (rs0 || rs1) {   // block-uniform
-                for (int sl = 0; sl < 2; ++sl) {
-                    if (sl == 0 ? !rs0 : !rs1) continue;
-                    const f32x4* src = reinterpret_cast<const f32x4*>(p.packed + (size_t)(sl == 0 ? sk0 : sk1) * PK_FLOATS);
-                    f32x4* dst = reinterpret_cast<f32x4*>(smem + sl * PK_FLOATS);
-                    for (int i = threadIdx.x; i < PK_FLOATS / 4; i += blockDim.x) dst[i] = src[i];
-                }
-                __syncthreads();
-            }
-        }
-#if ACN_DIAG_NOSLOTS  // diagnostic build only: every expert from global memory
-        const int k0 = -1, k1 = -1;
-#else
+        const int rclear = rbuf == 0 ? 2 : rbuf - 1;   // (q + 2) % 3
+        if (threadIdx.x < kMaxK) cnt[rclear][threadIdx.x] = 0;
+        rbuf = rbuf == 2 ? 0 : rbuf + 1;
+        choose_slots(cq, cfg.K, p.packed, smem, threadIdx.x, sk0, sk1);
         const int k0 = sk0, k1 = sk1;
-#endif
-        if (live) { SL_MARK(ray, 2) }
         if (live) {
             const bool single = (m & kSingleRay) != 0u;
             const int k_single = __builtin_ctz(m | kSingleRay);
@@ -1655,14 +1373,14 @@ __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) re
                        [&](int sc_, float px, float py, float pz, const float (&shv)[8], uint32_t& folded, float& yr, float& yg,
                            float& yb, float& ys) {
                            (void)sc_;
-                           slots_field<INTERP, ROUTE, FOLD>(cfg, p, smem, cb, cbg, k0, k1, single, k_single, px, py,
-                                                            pz, shv, folded, lane, yr, yg, yb, ys);
+                           slots_field<INTERP, ROUTE>(cfg, p, smem, cb, cbg, k0, k1, single, k_single, px, py, pz, shv,
+                                                      folded, lane, yr, yg, yb, ys);
 #if ACN_SLOTS_CHECK  // diagnostic build only: the tile evaluated again with every fold redone; a differing lane
                      // poisons its sample (NaN rgb: tools/dbg/selfcheck.py)
                            uint32_t f2 = 0u;
                            float cr, cg, cbb, cs;
-                           slots_field<INTERP, ROUTE, FOLD>(cfg, p, smem, cb, cbg, k0, k1, single, k_single, px, py,
-                                                            pz, shv, f2, lane, cr, cg, cbb, cs);
+                           slots_field<INTERP, ROUTE>(cfg, p, smem, cb, cbg, k0, k1, single, k_single, px, py, pz, shv,
+                                                      f2, lane, cr, cg, cbb, cs);
                            if (__float_as_uint(cr) != __float_as_uint(yr) || __float_as_uint(cg) != __float_as_uint(yg) ||
                                __float_as_uint(cbb) != __float_as_uint(yb) || __float_as_uint(cs) != __float_as_uint(ys)) {
 #if ACN_SLOTS_CHECK > 1   // record the mismatch (tools/dbg/selfcheck.py --detail)
@@ -1679,14 +1397,13 @@ __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) re
                            }
 #endif
                        });
-            SL_MARK(ray, 5)
         }
     }
 }
 
 // Routed render in depth tiles (render_wss_kernel: C3 / C4 without early termination).  render_slots_kernel gives
 // every wave one ray and its 32-sample tiles; here, as in render_ws_kernel, the 8 rays of a workgroup round are
-// cut into tiles of R rays x 32 / R consecutive samples (ACN_WSS_DTILE), so a wave's hash gathers come from
+// cut into tiles of R rays x 32 / R consecutive samples (kWssDtile8 / 16), so a wave's hash gathers come from
 // neighbouring rays at nearby depths.  Per round: every wave routes its ray's samples (ray_expert_mask), the
 // counts pick the two most needed experts for the LDS slots (render_slots_kernel's rule; the others are read
 // from the packed images in global memory), the waves take tiles from an LDS counter and put each sample's
@@ -1694,27 +1411,17 @@ __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) re
 // (composite_ray_lds).  A tile mixes rays, so colour layer 0 runs unfolded on each lane's own SH rows, SH k-steps
 // first (field_tile SHFIRST: bit for bit the folded layer), and the blend is the general path (for a
 // single-expert ray 0 + y * 1.0f == y): every output equals render_slots_kernel's (tests/test_k8.py).
-#ifndef ACN_RENDER_WSS
-#define ACN_RENDER_WSS 1
-#endif
 // Rounds (RW = rays per round, LDS ybuf = RW x kWssMaxS(RW) samples x 16 B = 32 KB beside the two expert images):
 // 16 rays (two per wave) in tiles of 16 rays x 2 samples up to S = 128, else 8 rays in tiles of 8 x 4.  C4-S96:
 // 3.12e9 (8 / 8 x 4) -> 3.17e9 (16 / 8 x 4) -> 3.27e9 (16 / 16 x 2) ray-samples/s (profiles/r06ac_wss_rounds_ab.jsonl)
-#ifndef ACN_WSS_DTILE8
-#define ACN_WSS_DTILE8 8     // rays per tile in 8-ray rounds
-#endif
-#ifndef ACN_WSS_DTILE16
-#define ACN_WSS_DTILE16 16   // rays per tile in 16-ray rounds
-#endif
-#ifndef ACN_WSS_RAYS16
-#define ACN_WSS_RAYS16 1     // 0: 8-ray rounds at every S
-#endif
+constexpr int kWssDtile8 = 8;     // rays per tile in 8-ray rounds
+constexpr int kWssDtile16 = 16;   // rays per tile in 16-ray rounds
 constexpr int kWssMaxS(int rw) { return rw == 8 ? kWsMaxS : 128; }
 template <int INTERP, int ROUTE, int RW>
 __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) render_wss_kernel(FieldCfg cfg, BgArgs bg, RenderParams p) {
     constexpr int kWssRays = RW, kWssPerWave = RW / (ACN_SLOTS_THREADS / 64), kMaxS = kWssMaxS(RW);
-    constexpr int R = RW == 8 ? ACN_WSS_DTILE8 : ACN_WSS_DTILE16, D = 32 / R, NG = kWssRays / R;
-    static_assert(kWssRays % R == 0 && 32 % R == 0, "ACN_WSS_DTILE*: rays per tile");
+    constexpr int R = RW == 8 ? kWssDtile8 : kWssDtile16, D = 32 / R, NG = kWssRays / R;
+    static_assert(kWssRays % R == 0 && 32 % R == 0, "kWssDtile*: rays per tile");
     __shared__ __attribute__((aligned(16))) float smem[2 * PK_FLOATS];
     __shared__ __attribute__((aligned(16))) f32x4 ybuf[kWssRays * kMaxS];
     static_assert(kWssPerWave >= 1 && kWssRays == kWssPerWave * (ACN_SLOTS_THREADS / 64), "rays per round");
@@ -1744,35 +1451,11 @@ __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) re
                     if ((m >> k) & 1u) atomicAdd(&cnt[k], 1);
         }
         __syncthreads();
-        {   // the two most needed experts (render_slots_kernel's choice and slot keeping)
-            int b0 = -1, b1 = -1;
-            for (int k = 0; k < cfg.K; ++k) {
-                const int c = cnt[k];
-                if (c == 0) continue;
-                if (b0 < 0 || c > cnt[b0]) { b1 = b0; b0 = k; }
-                else if (b1 < 0 || c > cnt[b1]) b1 = k;
-            }
-            b0 = __builtin_amdgcn_readfirstlane(b0);
-            b1 = __builtin_amdgcn_readfirstlane(b1);
-            if (b0 == sk1 || b1 == sk0) { const int t = b0; b0 = b1; b1 = t; }
-            const bool rs0 = b0 >= 0 && b0 != sk0, rs1 = b1 >= 0 && b1 != sk1;
-            if (b0 >= 0) sk0 = b0;
-            if (b1 >= 0) sk1 = b1;
-            if (rs0 || rs1) {   // block-uniform
-                for (int sl = 0; sl < 2; ++sl) {
-                    if (sl == 0 ? !rs0 : !rs1) continue;
-                    const f32x4* src = reinterpret_cast<const f32x4*>(p.packed + (size_t)(sl == 0 ? sk0 : sk1) * PK_FLOATS);
-                    f32x4* dst = reinterpret_cast<f32x4*>(smem + sl * PK_FLOATS);
-                    for (int i = tid; i < PK_FLOATS / 4; i += blockDim.x) dst[i] = src[i];
-                }
-                __syncthreads();
-            }
-        }
+        choose_slots(cnt, cfg.K, p.packed, smem, tid, sk0, sk1);
         const int k0 = sk0, k1 = sk1;
         int gcur = -1, slot = 0;
-        float ox = 0.0f, oy = 0.0f, oz = 0.0f, dx = 0.0f, dy = 0.0f, dz = 0.0f, near = 0.0f, far = 0.0f;
+        RayIn ri{};
         float shv[8];
-        const float* jit = nullptr;
         for (;;) {
             int item = 0;
             if (lane == 0) item = __hip_atomic_fetch_add(&qhead, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1782,27 +1465,16 @@ __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) re
             if (g != gcur) {   // wave-uniform: this lane's ray of group g
                 slot = g * R + (j % R);
                 const int ls = slot < nr ? slot : nr - 1;
-                const int64_t rr = p.order ? (int64_t)p.order[base + ls] : base + ls;
-                const float* rp = p.rays + rr * 8;
-                ox = rp[0], oy = rp[1], oz = rp[2], dx = rp[3], dy = rp[4], dz = rp[5];
-                near = rp[6], far = rp[7];
-                jit = p.jitter ? p.jitter + rr * S : nullptr;
+                ri = load_ray(p, p.order ? (int64_t)p.order[base + ls] : base + ls);
                 float sh[16];
-                dir_sh(dx, dy, dz, sh);
+                dir_sh(ri.dx, ri.dy, ri.dz, sh);
                 sh_rows_for_half(sh, h, shv);
                 gcur = g;
             }
             const int s = q * D + j / R;
             const int sc = s < S ? s : S - 1;
-            float t;
-            if (!jit) {
-                const int i0 = sc < S - 1 ? sc : S - 2;
-                const float ta = tlin_sel(near, far, i0, S, step), tb = tlin_sel(near, far, i0 + 1, S, step);
-                t = sc < S - 1 ? ta : tb;
-            } else {
-                t = tval(near, far, sc, S, jit);
-            }
-            const float px = ox + dx * t, py = oy + dy * t, pz = oz + dz * t;
+            const float t = sample_t(ri.near, ri.far, sc, S, step, ri.jit);
+            const float px = ri.ox + ri.dx * t, py = ri.oy + ri.dy * t, pz = ri.oz + ri.dz * t;
             const RouteState st = route_prep<ROUTE>(cfg, px, py, pz);
             float yr = 0.0f, yg = 0.0f, yb = 0.0f, ys = 0.0f;
             for (int k = 0; k < cfg.K; ++k) {
@@ -1869,9 +1541,6 @@ __device__ __forceinline__ int lanes_below(uint64_t m) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 constexpr int kRtThreads = 512;   // ep_field_kernel: two workgroups per CU (16 waves)
-#ifndef ACN_EP_BANDS
-#define ACN_EP_BANDS 1                // ep_field_kernel: XCD bands over each expert's wave-tiles
-#endif
 constexpr int kRtWaves = kRtThreads / 64;
 constexpr int kEpMaxSeg = 1024;   // W * E segments of the compact received layout (ep_field_kernel)
 
@@ -1917,7 +1586,7 @@ __global__ void __launch_bounds__(kRtThreads, 4) ep_field_kernel(FieldCfg cfg, c
         // XCD bands (as render_kernel): with the grid a multiple of 8, XCD x takes the x-th contiguous eighth of the
         // expert's wave-tiles, so consecutive records (a ray's samples, neighbouring rays) share one XCD's L2
         int64_t g0 = (int64_t)blockIdx.x * kRtWaves + wave, gend = T, gstep = G;
-        if (ACN_EP_BANDS && (gridDim.x & 7) == 0) {
+        if ((gridDim.x & 7) == 0) {
             const int64_t chunk = (T + 7) >> 3;
             const int64_t lo = min(T, (int64_t)(blockIdx.x & 7) * chunk);
             gend = min(T, lo + chunk);
@@ -2167,18 +1836,6 @@ __global__ void __launch_bounds__(256) volume_render_bwd_kernel(
 // tested sizes, not by construction).
 constexpr int kCmThreads = 256;
 constexpr int kCmMaxBlocks = 4096;
-#ifndef ACN_CM_PROF
-#define ACN_CM_PROF 0   // diagnostic build: per-ray section timestamps (acn_debug_cmprof_fetch)
-#endif
-#if ACN_CM_PROF
-__device__ unsigned long long g_cmprof[4096 * 8];
-__device__ unsigned long long g_cmblk[4096 * 4];
-#define CM_MARK(i) if (lane == 0 && ray < 4096) g_cmprof[ray * 8 + (i)] = wall_clock64();
-#define CM_BLK(i) if (threadIdx.x == 0 && blockIdx.x < 4096) g_cmblk[blockIdx.x * 4 + (i)] = wall_clock64();
-#else
-#define CM_MARK(i)
-#define CM_BLK(i)
-#endif
 constexpr int kCmMaxS = 1024;   // the per-wave LDS rows of S float4 + S float (4 waves: 80 KB at S = 1024)
 // a wave's LDS writes visible to its own later reads (in-order LDS; keeps the compiler from reordering)
 __device__ __forceinline__ void wave_lds_sync() {
@@ -2198,7 +1855,6 @@ __global__ void __launch_bounds__(kCmThreads) composite_mse_train_kernel(
     __shared__ double red[kCmThreads / 64];
     __shared__ bool last;
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5, wv = threadIdx.x >> 6;
-    CM_BLK(0)
     float4* row = cm_rows + wv * S;
     float* trow = reinterpret_cast<float*>(cm_rows + (kCmThreads / 64) * S) + wv * S;
     const int64_t nw = (int64_t)gridDim.x * (kCmThreads >> 6);
@@ -2217,7 +1873,6 @@ __global__ void __launch_bounds__(kCmThreads) composite_mse_train_kernel(
         for (int k = 0; k < ACN_MAX_EXPERTS; ++k) w[u][k] = pp[u][k] >= 0 ? pw[pp[u][k]] : 0.0f;
     };
     for (int64_t ray = (int64_t)blockIdx.x * (kCmThreads >> 6) + wv; ray < N; ray += nw) {
-        CM_MARK(0)
         const float dx = rays[8 * ray + 3], dy = rays[8 * ray + 4], dz = rays[8 * ray + 5];
         const int64_t m0 = ray * S;
         const float* tg = tv + m0;
@@ -2251,13 +1906,11 @@ __global__ void __launch_bounds__(kCmThreads) composite_mse_train_kernel(
                 row[s] = acc;
             }
         }
-        CM_MARK(1)
         const float gt3[3] = {gt[3 * ray], gt[3 * ray + 1], gt[3 * ray + 2]};
         float c[3];
         background(bg, dx, dy, dz, lane, c);
         if (lane < 3) dirs_out[3 * ray + lane] = lane == 0 ? dx : (lane == 1 ? dy : dz);
         wave_lds_sync();
-        CM_MARK(2)
         auto fetch = [&](int sc) { return row[sc]; };
         float r, g, b, dd, a;
         vr_fwd_ray(fetch, trow, S, 0, 0, 1.0f, j, h, nullptr, r, g, b, dd, a);
@@ -2276,7 +1929,6 @@ __global__ void __launch_bounds__(kCmThreads) composite_mse_train_kernel(
             rgb_out[3 * ray + 1] = pr[1];
             rgb_out[3 * ray + 2] = pr[2];
         }
-        CM_MARK(3)
         // the backward's second sweep reads sample s, then writes its gradient over it (same lane, same tile)
         const double acc = vr_bwd_ray(fetch, [&](int s, float4 o) { row[s] = o; }, trow, S, 1.0f, gq[0], gq[1],
                                       gq[2], 0.0f, 0.0f, c[0], c[1], c[2], nullptr, j, h);
@@ -2287,7 +1939,6 @@ __global__ void __launch_bounds__(kCmThreads) composite_mse_train_kernel(
             g_bg[3 * ray + 2] = omb * gq[2];
         }
         wave_lds_sync();
-        CM_MARK(4)
         // blend backward (blend_bwd_kernel): every pair slot of sample s gets dL/d(rgb_sigma)_s * w
         for (int s0 = 0; s0 < S; s0 += 128) {
 #pragma unroll
@@ -2303,14 +1954,11 @@ __global__ void __launch_bounds__(kCmThreads) composite_mse_train_kernel(
             }
         }
         wave_lds_sync();
-        CM_MARK(5)
     }
-    CM_BLK(1)
     // padding slots of the pair segments (pidx < 0 below the live count): zero gradients, as blend_bwd_kernel
     const int64_t nl = live ? (live[0] < P ? live[0] : P) : P;
     for (int64_t p = (int64_t)blockIdx.x * kCmThreads + threadIdx.x; p < nl; p += (int64_t)gridDim.x * kCmThreads)
         if (pidx[p] < 0) gy[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    CM_BLK(2)
     if (lane == 0) red[wv] = lsum;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -2336,7 +1984,6 @@ __global__ void __launch_bounds__(kCmThreads) composite_mse_train_kernel(
             loss[0] = (float)(t / (double)n);
             counter[0] = 0u;
         }
-        CM_BLK(3)
     }
 }
 
@@ -2582,9 +2229,6 @@ __global__ void __launch_bounds__(256) sample_train_kernel(const float* __restri
 // go to the last cell.
 #define ACN_ORDER_MAX 8192
 #define ACN_ORDER_BINS 4096
-#ifndef ACN_ORDER_COUNTING
-#define ACN_ORDER_COUNTING 1  // stable counting sort with per-cell ranks (0: the two stable radix passes always)
-#endif
 __device__ __forceinline__ uint32_t spread6(uint32_t v) {
     v &= 63u;
     v = (v | (v << 4)) & 0x30Fu;
@@ -2707,10 +2351,6 @@ __global__ void __launch_bounds__(1024) ray_order_kernel(const float* __restrict
             }
         }
     }
-#if ACN_ORDER_DIAG == 3  // diagnostic only (tools/order_diag.sh): loads, then the identity order
-    for (int i = tid; i < N; i += 1024) order[i] = i + (int)(sx * 0.0f);
-    return;
-#endif
     block_reduce3<0>(sx, sy, sz, red);
     const float mn = sqrtf(sx * sx + sy * sy + sz * sz);
     float mx = 0.0f, my = 0.0f, mz = 1.0f;
@@ -2743,17 +2383,9 @@ __global__ void __launch_bounds__(1024) ray_order_kernel(const float* __restrict
         cok[q] = i < N && coords(i, cu[q], cv[q]);
         if (cok[q]) umin = fminf(umin, cu[q]), umax = fmaxf(umax, cu[q]), vmin = fminf(vmin, cv[q]), vmax = fmaxf(vmax, cv[q]);
     }
-#if ACN_ORDER_DIAG == 2  // diagnostic only: + mean direction and the coordinate pass, identity order
-    for (int i = tid; i < N; i += 1024) order[i] = i + (int)(umin * 0.0f + umax * 0.0f);
-    return;
-#endif
-#if ACN_ORDER_DIAG == 1  // diagnostic only: fixed range instead of the bounding-box reduction
-    umin = -2.0f, vmin = -2.0f, umax = 2.0f, vmax = 2.0f;
-#else
     umin = -umin, vmin = -vmin;  // one max-reduction for all four
     block_reduce4max(umin, vmin, umax, vmax, red);
     umin = -umin, vmin = -vmin;
-#endif
     const float su = umax > umin ? 63.999f / (umax - umin) : 0.0f;
     const float sv = vmax > vmin ? 63.999f / (vmax - vmin) : 0.0f;
 #pragma unroll
@@ -2769,7 +2401,6 @@ __global__ void __launch_bounds__(1024) ray_order_kernel(const float* __restrict
         cell_of[i] = (uint16_t)c;
     }
     __syncthreads();  // dir[] is free from here on
-#if ACN_ORDER_COUNTING
     // Counting sort by cell, made stable per cell afterwards: histogram (LDS atomics), scan, an unordered
     // scatter of the indices into their cell's slice, then every element's rank inside its slice = the number
     // of slice members with a smaller index (cells hold a few rays each: 4096 rays over 4096 cells).  A cell
@@ -2821,7 +2452,6 @@ __global__ void __launch_bounds__(1024) ray_order_kernel(const float* __restrict
         }
         __syncthreads();
     }
-#endif
     uint16_t* key1 = reinterpret_cast<uint16_t*>(&dir[0][0]);
     uint16_t* idx1 = reinterpret_cast<uint16_t*>(&dir[1][0]);
     radix_pass6<false>(cell_of, nullptr, 0, N, cnt, wsum, key1, idx1, nullptr);
@@ -2872,6 +2502,26 @@ extern "C" int acn_field_fwd(const float* x, int64_t M, int64_t ld, const acn_ex
     return acn_check_launch("acn_field_fwd");
 }
 
+namespace {
+// The stratified render's kernel for one (interpolation, LDS-resident experts, routing) case.  Without early
+// termination (tau <= 0) and with S inside their LDS sample buffers, the depth-tiled kernels take the launch:
+// render_ws_kernel for one expert, render_wss_kernel for K > 2 (KL == 0; 16-ray rounds while S fits them).
+template <int I, int KL, int R>
+void launch_render(dim3 grid, hipStream_t s, const FieldCfg& cfg, const BgArgs& b, const RenderParams& p) {
+    const bool whole_rays = !(p.tau > 0.0f);
+    if constexpr (KL == 0) {   // routed, K > 2: two expert slots in LDS
+        const dim3 block(ACN_SLOTS_THREADS);
+        if (whole_rays && p.S <= kWssMaxS(16)) hipLaunchKernelGGL((render_wss_kernel<I, R, 16>), grid, block, 0, s, cfg, b, p);
+        else if (whole_rays && p.S <= kWssMaxS(8)) hipLaunchKernelGGL((render_wss_kernel<I, R, 8>), grid, block, 0, s, cfg, b, p);
+        else hipLaunchKernelGGL((render_slots_kernel<I, R>), grid, block, 0, s, cfg, b, p);
+    } else {
+        const dim3 block(1024);
+        if (R == 0 && whole_rays && p.S <= kWsMaxS) hipLaunchKernelGGL(render_ws_kernel<I>, grid, block, 0, s, cfg, b, p);
+        else hipLaunchKernelGGL((render_kernel<I, KL, R>), grid, block, 0, s, cfg, b, p);
+    }
+}
+}  // namespace
+
 extern "C" int acn_render_stratified_fwd(const float* rays, int64_t N, int S, const float* jitter,
                                          const acn_expert* experts, const acn_routing* routing, int active_module,
                                          const acn_background* bg, float sigma_scale, float tau, void* workspace,
@@ -2905,28 +2555,13 @@ extern "C" int acn_render_stratified_fwd_ordered(const float* rays, int64_t N, i
     RenderParams p{rays, N, S, jitter, (const float*)workspace, sigma_scale, tau, rgb, depth, weights, acc, nullptr};
     int64_t wgs = (N + 15) / 16;
     if ((num_cus() & 7) == 0) wgs = (wgs + 7) & ~(int64_t)7;  // whole XCD bands (render_kernel)
-    const dim3 grid((unsigned)(wgs < num_cus() ? wgs : num_cus())), block(1024);
-    const bool slots = ACN_SLOTS && cfg.routing != 0 && K != 2;  // render_slots_kernel keeps its own order
+    const dim3 grid((unsigned)(wgs < num_cus() ? wgs : num_cus()));
+    const bool slots = cfg.routing != 0 && K != 2;  // render_slots_kernel keeps its own order
     if (order_scratch && !slots && N <= ACN_ORDER_MAX && order_bytes >= (size_t)N * sizeof(int32_t)) {
         hipLaunchKernelGGL(ray_order_kernel, dim3(1), dim3(1024), 0, s, rays, (int)N, (int32_t*)order_scratch);
         p.order = (const int32_t*)order_scratch;
     }
-    const bool wss = ACN_RENDER_WSS && S <= kWssMaxS(8) && !(tau > 0.0f);   // routed, no early termination: depth tiles
-    const bool wss16 = ACN_WSS_RAYS16 && S <= kWssMaxS(16);
-#define ACN_RENDER_LAUNCH(I, KL, R)                                                                    \
-    do {                                                                                              \
-        if (ACN_SLOTS && KL == 0 && R != 0 && wss && wss16) hipLaunchKernelGGL((render_wss_kernel<I, (R == 0 ? 1 : R), 16>), grid, dim3(ACN_SLOTS_THREADS), 0, s, cfg, b, p); \
-        else if (ACN_SLOTS && KL == 0 && R != 0 && wss) hipLaunchKernelGGL((render_wss_kernel<I, (R == 0 ? 1 : R), 8>), grid, dim3(ACN_SLOTS_THREADS), 0, s, cfg, b, p); \
-        else if (ACN_SLOTS && KL == 0 && R != 0) hipLaunchKernelGGL((render_slots_kernel<I, (R == 0 ? 1 : R)>), grid, dim3(ACN_SLOTS_THREADS), 0, s, cfg, b, p); \
-        else hipLaunchKernelGGL((render_kernel<I, KL, R>), grid, block, 0, s, cfg, b, p);            \
-    } while (0)
-    if (ACN_RENDER_WS && cfg.routing == 0 && S <= kWsMaxS && !(tau > 0.0f)) {
-        // one expert, no early termination: the workgroup shares its rays' field tiles (bit-identical outputs)
-        if (interp == 1) hipLaunchKernelGGL(render_ws_kernel<1>, grid, block, 0, s, cfg, b, p);
-        else if (interp == 0) hipLaunchKernelGGL(render_ws_kernel<0>, grid, block, 0, s, cfg, b, p);
-        else hipLaunchKernelGGL(render_ws_kernel<2>, grid, block, 0, s, cfg, b, p);
-        return acn_check_launch("acn_render_stratified_fwd");
-    }
+#define ACN_RENDER_LAUNCH(I, KL, R) launch_render<I, KL, R>(grid, s, cfg, b, p)
     ACN_DISPATCH(ACN_RENDER_LAUNCH);
 #undef ACN_RENDER_LAUNCH
     return acn_check_launch("acn_render_stratified_fwd");
@@ -3067,12 +2702,12 @@ struct OccRenderParams {
 
 // meta_container blend of render_rays_occ (:426-449): s = clamp_min(sum_k W_k sigma_k, 1e-12),
 // rgb = sum_k (W_k sigma_k) rgb_k / s, experts evaluated only where W_k > 1e-8.
-template <int INTERP, int ROUTE, bool FOLD>
+template <int INTERP, int ROUTE>
 __device__ __forceinline__ void container_tile_occ(const FieldCfg& cfg, const float* Wbase, float px, float py,
                                                    float pz, const float (&shv)[8], float* cb, uint32_t* folded,
                                                    int lane, float& yr, float& yg, float& yb, float& ys) {
     if (ROUTE == 0) {
-        container_tile<INTERP, 0, FOLD>(cfg, Wbase, px, py, pz, shv, cb, folded, lane, yr, yg, yb, ys);
+        container_tile<INTERP, 0, true>(cfg, Wbase, px, py, pz, shv, cb, folded, lane, yr, yg, yb, ys);
         return;
     }
     const RouteState st = route_prep<ROUTE>(cfg, px, py, pz);
@@ -3082,13 +2717,13 @@ __device__ __forceinline__ void container_tile_occ(const FieldCfg& cfg, const fl
         const bool need = wk > 1e-8f;
         if (__ballot(need) == 0ull) continue;
         const float* Wk = Wbase + (size_t)k * PK_FLOATS;
-        float* cbk = FOLD ? cb + k * 64 : nullptr;
-        if (FOLD && !((*folded >> k) & 1u)) {
+        float* cbk = cb + k * 64;
+        if (!((*folded >> k) & 1u)) {
             fold_sh_bias(Wk, shv, lane, cbk);
             *folded |= 1u << k;
         }
         float r, g, b, s;
-        field_tile<INTERP, FOLD>(Wk, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbk, lane, r, g, b, s);
+        field_tile<INTERP, true>(Wk, cfg.ex[k], cfg.log2T, px, py, pz, shv, cbk, lane, r, g, b, s);
         s = trunc_exp(s);
         if (need) {
             const float ws = wk * s;
@@ -3168,10 +2803,9 @@ __device__ __forceinline__ void render_ray_packed(const OccRenderParams& p, cons
 
 template <int INTERP, int KL, int ROUTE>
 __global__ void __launch_bounds__(1024, 4) occ_render_kernel(FieldCfg cfg, BgArgs bg, OccRenderParams p) {
-    constexpr bool FOLD = ACN_SHFOLD != 0;
     constexpr int KF = ROUTE == 0 ? 1 : (KL == 2 ? 2 : kMaxK);
     __shared__ __attribute__((aligned(16))) float smem[(KL > 0 ? KL : 1) * PK_FLOATS];
-    __shared__ __attribute__((aligned(16))) float cbuf[FOLD ? 16 * KF * 64 : 4];
+    __shared__ __attribute__((aligned(16))) float cbuf[16 * KF * 64];
     const float* W = p.packed;
     if (KL > 0) {
         stage_weights<KL>(smem, p.packed);
@@ -3179,14 +2813,14 @@ __global__ void __launch_bounds__(1024, 4) occ_render_kernel(FieldCfg cfg, BgArg
     }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* cb = FOLD ? cbuf + wave * KF * 64 : nullptr;
+    float* cb = cbuf + wave * KF * 64;
     const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t ray = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave; ray < p.N; ray += nw) {
         render_ray_packed(p, bg, ray, lane,
                           [&](float px, float py, float pz, const float (&shv)[8], uint32_t& folded, float& yr,
                               float& yg, float& yb, float& ys) {
-                              container_tile_occ<INTERP, ROUTE, FOLD>(cfg, W, px, py, pz, shv, cb, &folded, lane, yr,
-                                                                      yg, yb, ys);
+                              container_tile_occ<INTERP, ROUTE>(cfg, W, px, py, pz, shv, cb, &folded, lane, yr, yg,
+                                                                yb, ys);
                           });
     }
 }
@@ -3292,25 +2926,6 @@ extern "C" int acn_ep_composite(const float* rays, int64_t N, int S, const float
     return acn_check_launch("acn_ep_composite");
 }
 
-#if ACN_SLOTS_PROF
-extern "C" int acn_debug_slprof_fetch(unsigned long long* host, int max_rays) {
-    const int m = max_rays < kSlProfRays ? max_rays : kSlProfRays;
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_slprof), (size_t)m * 6 * sizeof(unsigned long long)) == hipSuccess
-               ? m : -1;
-}
-#endif
-#if ACN_CM_PROF
-extern "C" int acn_debug_cmprof_fetch(unsigned long long* host, int max_rays) {
-    const int m = max_rays < 4096 ? max_rays : 4096;
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_cmprof), (size_t)m * 8 * sizeof(unsigned long long)) == hipSuccess
-               ? m : -1;
-}
-extern "C" int acn_debug_cmblk_fetch(unsigned long long* host, int max_blocks) {
-    const int m = max_blocks < 4096 ? max_blocks : 4096;
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_cmblk), (size_t)m * 4 * sizeof(unsigned long long)) == hipSuccess
-               ? m : -1;
-}
-#endif
 #if ACN_FIELD_CHECK
 extern "C" int acn_debug_fchk_fetch(uint32_t* host) {
     if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fchk), 3 * sizeof(uint32_t)) != hipSuccess) return -1;

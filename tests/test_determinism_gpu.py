@@ -1,8 +1,8 @@
 """Run-to-run determinism of the MFMA kernels: the same inputs give bitwise the same outputs on
-every call.  Round 4 recorded two one-off 1-ulp render differences whose cause was a VALU -> MFMA operand hazard
-(v_cvt_pk_f16_f32 writing an fp16 B fragment two wait states before the MFMA that reads it).  Every fp16
-fragment now passes the operand fence (acn_device.h); these tests repeat the cases where the differences were
-seen, and the training MLP kernels (same split -> MFMA idiom, tolerance-tested elsewhere), many times.
+every call.  Round 4 recorded two one-off 1-ulp render differences; round 5 took them for a VALU -> MFMA operand
+hazard, round 6 found their cause in the hash gathers issued as global loads, which are buffer loads now
+(DESIGN.md §4l).  These tests repeat the cases where the differences were seen, and the training MLP kernels (same
+split -> MFMA idiom, tolerance-tested elsewhere), many times.
 
 Reference behaviour: rays are rendered independently and deterministically (nerfs/ray_rendering.py:290-345);
 the training MLP is MetaNGP's chain (models/inr/meta_ngp.py:171-241)."""

@@ -4,9 +4,8 @@ Compiles render.hip and mlp_train.hip to gfx950 assembly with the Makefile's fla
 GPU) and runs tools/hazard_audit.py over every kernel: no MFMA may have a VALU write of its A / B / C operands, a
 reader or writer of its result, a partial-overlap accumulator or a write of its C operand within the wait states
 gfx950 requires (LLVM's gfx940 rules + 1, tools/hazard_audit.py REQ), counted along every control-flow path with
-inline-asm contents as the instructions they hold.  (The round-5 operand fence, 16 states before every fp16 B
-operand, is compiled out since round 6: the differences it was meant for came from the hash gathers, DESIGN.md §4l;
-the gap hipcc leaves, >= 2 states, is what the box probe requires, 1.)"""
+inline-asm contents as the instructions they hold.  (The gap hipcc leaves before an fp16 B operand, >= 2 states, is
+what the box probe requires, 1)"""
 import os
 import re
 import shutil

@@ -1,9 +1,8 @@
 """Self-check builds of the fused render: every 32-sample field tile is evaluated twice and a
 lane whose second evaluation differs bitwise poisons its sample (NaN rgb), so a ray with a NaN colour is a
 run-to-run difference caught in the act.
-  ACN_WS_CHECK=1     render_ws_kernel (one expert): the second evaluation runs colour layer 0 unfolded (SH k-step
-                     first, bit for bit the per-ray fold + folded layer), so the fold is checked too
   ACN_SLOTS_CHECK=1  render_slots_kernel's per-wave path (K > 2): the second evaluation redoes every fold
+  ACN_FIELD_CHECK=1  the hash encoding of that path evaluated twice, differing lanes counted and recorded
 Run with ACNERF_LIB=<variant .so> (tools/build_variants.sh).  Cases: the reference K = 4 fixture's rays with
 active_module 2 (one expert) and soft routing, and the K = 8 fixture, 4096 rays, S = 64 / 200 / 256, eval and
 training jitter, `reps` renders each."""

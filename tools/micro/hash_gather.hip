@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(256) gather_kernel(const float* __restrict__ x
                 const int lv = i + 8 * h;
                 const float rs = res.r[lv];
                 const float2* tl = reinterpret_cast<const float2*>(table) + ((size_t)lv << log2T);
-                acn::hash_issue<1, 0>(tl, px * rs, py * rs, pz * rs, mask, pp);
+                acn::hash_issue<1>(tl, px * rs, py * rs, pz * rs, mask, pp);
             };
 #pragma unroll
             for (int l = 0; l < D - 1; ++l) issue(l, pend[l]);
