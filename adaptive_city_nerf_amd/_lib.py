@@ -105,6 +105,8 @@ SIGNATURES = {
                      C.c_int),
     "acn_ray_directions": ([i32, i32, f32, f32, f32, f32, i32, vp, vp], C.c_int),
     "acn_rays_from_dirs": ([vp, i64, vp, vp, f32, f32, f32, f32, f32, vp, vp], C.c_int),
+    "acn_rays_from_dirs_bwd_workspace_bytes": ([i64], C.c_size_t),
+    "acn_rays_from_dirs_bwd": ([vp, i64, vp, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "acn_ray_aabb": ([vp, vp, i64, vp, f32, f32, f32, vp, vp, vp], C.c_int),
     "acn_clamp_rays": ([vp, i64, i32, i32, f32, i32, f32, f32, f32, vp, vp], C.c_int),
     "acn_routing_fwd": ([vp, i64, i64, vp, vp, vp, vp], C.c_int),
@@ -154,6 +156,8 @@ SIGNATURES = {
     "acn_sample_stratified": ([vp, i64, C.c_int, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp], C.c_int),
     "acn_mlp_train_bwd_dw": ([vp, vp, vp, vp, i64, vp, vp, vp, vp, vp], C.c_int),
     "acn_mlp_train_bwd_dw_img": ([vp, vp, vp, vp, i64, vp, vp, vp, vp, vp], C.c_int),
+    "acn_mlp_train_bwd_input": ([vp, vp, vp, vp, i64, vp, vp, vp, vp, vp], C.c_int),
+    "acn_mlp_train_bwd_input_img": ([vp, vp, vp, vp, i64, vp, vp, vp, vp], C.c_int),
     # routed.hip
     "acn_routed_workspace_bytes": ([i64, i32], C.c_size_t),
     "acn_routed_count": ([vp, i64, i32, vp, vp, i32, vp, vp, vp, sz, vp], C.c_int),
@@ -191,10 +195,11 @@ SIGNATURES = {
     # clusters.hip
     "acn_voronoi_route": ([vp, i64, i32, vp, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp], C.c_int),
 }
-# the exact-fp32 training MLP (suffix _exact) and the reference's use_amp arithmetic (suffix _amp): the same ten
+# the exact-fp32 training MLP (suffix _exact) and the reference's use_amp arithmetic (suffix _amp): the same twelve
 # entry points (mlp_train.hip built three times)
 MLP_ENTRY_POINTS = ("acn_mlp_workspace_bytes", "acn_mlp_train_fwd", "acn_mlp_train_bwd", "acn_mlp_dw_workspace_bytes",
-                    "acn_mlp_train_bwd_dw", "acn_mlp_train_bwd_dw_img", "acn_mlp_pairs_workspace_bytes", "acn_mlp_pack_pairs",
+                    "acn_mlp_train_bwd_dw", "acn_mlp_train_bwd_dw_img", "acn_mlp_train_bwd_input",
+                    "acn_mlp_train_bwd_input_img", "acn_mlp_pairs_workspace_bytes", "acn_mlp_pack_pairs",
                     "acn_mlp_train_fwd_pairs", "acn_mlp_train_bwd_dw_pairs")
 SIGNATURES.update({n + sfx: SIGNATURES[n] for n in MLP_ENTRY_POINTS for sfx in ("_exact", "_amp")})
 

@@ -8,7 +8,9 @@
 //                      inputs the weight gradients need, each with a ones column (the bias term);
 //   acn_mlp_train_bwd: one launch -> d(hash features) (M, 32) and every layer's output gradient
 //                      (after the ReLU / sigmoid / trunc_exp derivative);
-// then one GEMM per layer on the caller's side gives [dW | db] = dY^T . [X | 1] (large-K GEMMs).
+// then one GEMM per layer on the caller's side gives [dW | db] = dY^T . [X | 1] (large-K GEMMs);
+//   acn_mlp_train_bwd_dw: the fused backward (forward re-run in registers, [dW | db] on MFMA, no saved activations);
+//   acn_mlp_train_bwd_input: the input gradients alone (dL/dh0, dL/dsh) for frozen weights, one launch.
 //
 // Execution: one wave per 32-sample tile, lanes (sample j = lane & 31, half h = lane >> 5).  Every
 // layer is Y^T = W . X^T on v_mfma_f32_32x32x2_f32 (exact fp32 fma chains) with the layer input in the
@@ -2004,6 +2006,79 @@ __global__ void __launch_bounds__(256) mlp_dw_reduce_pairs_kernel(const float* _
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Input gradients with frozen weights (acn_mlp_train_bwd_input): dL/d(hash features) and dL/d(SH features) of
+// [sigmoid(color_mlp(cat(geo, sh))), trunc_exp(sigma_head)] (MetaNGP.forward, models/inr/meta_ngp.py:226-241, the
+// torch.cat of :207-211 included).  One wave per 32-sample tile re-runs the forward (the tile_forward of
+// mlp_fwd_kernel, so the activations are the forward's bit for bit) and then the dX chain of mlp_bwd_kernel /
+// dw_round with the ReLU masks taken from the live activations; rows 15..30 of d cin, which those kernels drop,
+// are the SH gradient.  Nothing is staged, reduced or saved: after the weight staging there is no barrier, no
+// LDS write, no atomic, and every output row depends on its own sample only.
+__global__ void __launch_bounds__(256) mlp_bwd_input_kernel(const float* __restrict__ img, const float* __restrict__ h0,
+                                                            const float* __restrict__ sh, const float* __restrict__ out,
+                                                            const float* __restrict__ gout, int64_t M,
+                                                            float* __restrict__ gh0, float* __restrict__ gsh) {
+    __shared__ __attribute__((aligned(16))) float Wl[L_FLOATS];
+    stage_weights(img, Wl);
+    __syncthreads();
+    const int lane0 = threadIdx.x & 63, j = lane0 & 31;
+    const int64_t ntiles = (M + 31) / 32;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+        const int64_t m = tile * 32 + j;
+        const bool ok = m < M;
+        const float* W = Wl + opaque_s(0);   // as mlp_fwd_kernel: the LDS weight reads stay inside the tile loop
+        const int lane = opaque_v(lane0), h = lane >> 5;
+        f32x16 A1[2], A2[2], Hd[1], Cin[1], C1[2], C2[2], Rg[1];
+        {
+            f32x16 X0[1];
+            tile_forward(W, h0, sh, m, ok, lane, X0, A1, A2, Hd, Cin, C1, C2, Rg);
+        }
+        f32x16 dRg[1], dHd[1];
+        dRg[0] = 0.0f;
+        float dsig = 0.0f;
+        if (ok) {
+            if (h == 0) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float y = out[m * 4 + c];
+                    dRg[0][c] = grad_rgb(gout[m * 4 + c], y);
+                }
+            } else {
+                dsig = grad_sigma(gout[m * 4 + 3], out[m * 4 + 3]);
+            }
+        }
+        f32x16 G2[2], G1[2], Gc[1];
+        bwd_layer<2, 1, 3, 32>(W + L_WC2, S64, dRg, G2, lane);
+        relu_mask<2>(G2, C2);
+        bwd_layer<2, 2, 64, 64>(W + L_WC1, S64, G2, G1, lane);
+        relu_mask<2>(G1, C1);
+        bwd_layer<1, 2, 64, 64>(W + L_WC0, S32, G1, Gc, lane);  // d cin: rows 0..14 = d geo, 15..30 = d SH
+        if (gsh && ok) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int f = rho(r, h);
+                if (f >= 15 && f < 31) gsh[m * 16 + (f - 15)] = Gc[0][r];
+            }
+        }
+        if (gh0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int f = rho(r, h);
+                dHd[0][r] = f < 15 ? Gc[0][r] : (f == 15 ? dsig : 0.0f);
+            }
+            f32x16 GA2[2], GA1[2], GH[1];
+            bwd_layer<2, 1, 16, 32>(W + L_WH, S64, dHd, GA2, lane);
+            relu_mask<2>(GA2, A2);
+            bwd_layer<2, 2, 64, 64>(W + L_W1, S64, GA2, GA1, lane);
+            relu_mask<2>(GA1, A1);
+            bwd_layer<1, 2, 64, 64>(W + L_W0, S32, GA1, GH, lane);
+            store_tiles<1>(gh0, 32, 0, 32, m, ok, h, GH);
+        }
+    }
+}
+
 MlpPtrs ptrs(const acn_mlp* w) {
     return MlpPtrs{w->w0, w->b0, w->w1, w->b1, w->wsh, w->bsh, w->wg, w->bg,
                    w->wc0, w->bc0, w->wc1, w->bc1, w->wc2, w->bc2};
@@ -2103,6 +2178,32 @@ extern "C" int ACN_MLP_API(acn_mlp_train_bwd_dw_img)(const float* h0, const floa
     }
     ACN_REQUIRE(h0 && sh && out && gout, "acn_mlp_train_bwd_dw_img: NULL pointer");
     return bwd_dw_launch(h0, sh, out, gout, M, img, dw, gh0, (float*)workspace + L_FLOATS, s);
+}
+
+// input gradients with frozen weights (mlp_bwd_input_kernel); workspace: acn_mlp_workspace_bytes(), the packed image
+extern "C" int ACN_MLP_API(acn_mlp_train_bwd_input)(const float* h0, const float* sh, const float* out, const float* gout,
+                                       int64_t M, const acn_mlp* w, float* gh0, float* gsh, void* workspace,
+                                       void* stream) {
+    ACN_REQUIRE(M >= 0 && w && workspace, "acn_mlp_train_bwd_input: bad arguments");
+    if (M == 0 || (!gh0 && !gsh)) return ACN_OK;
+    ACN_REQUIRE(h0 && sh && out && gout, "acn_mlp_train_bwd_input: NULL pointer");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(mlp_pack_kernel, dim3((L_FLOATS + 255) / 256), dim3(256), 0, s, ptrs(w), (float*)workspace);
+    hipLaunchKernelGGL(mlp_bwd_input_kernel, dim3(grid_for(M)), dim3(256), 0, s, (const float*)workspace, h0, sh, out,
+                       gout, M, gh0, gsh);
+    return acn_check_launch("acn_mlp_train_bwd_input");
+}
+
+// the same on the image acn_mlp_train_fwd packed into its workspace for the same weights (no pack, no workspace)
+extern "C" int ACN_MLP_API(acn_mlp_train_bwd_input_img)(const float* h0, const float* sh, const float* out,
+                                           const float* gout, int64_t M, const float* img, float* gh0, float* gsh,
+                                           void* stream) {
+    ACN_REQUIRE(M >= 0 && img, "acn_mlp_train_bwd_input_img: bad arguments");
+    if (M == 0 || (!gh0 && !gsh)) return ACN_OK;
+    ACN_REQUIRE(h0 && sh && out && gout, "acn_mlp_train_bwd_input_img: NULL pointer");
+    hipLaunchKernelGGL(mlp_bwd_input_kernel, dim3(grid_for(M)), dim3(256), 0, (hipStream_t)stream, img, h0, sh, out,
+                       gout, M, gh0, gsh);
+    return acn_check_launch("acn_mlp_train_bwd_input_img");
 }
 
 // ---------------------------------------------------------------------------------------------

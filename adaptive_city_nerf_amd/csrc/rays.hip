@@ -41,6 +41,71 @@ __global__ void __launch_bounds__(256) rays_from_dirs_kernel(const float* __rest
     r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = dw[0]; r[4] = dw[1]; r[5] = dw[2]; r[6] = tmin; r[7] = tmax;
 }
 
+// Backward of rays_from_dirs_kernel in the pose and the directions (_rays_cam_to_world, ray_sampling.py:10-24:
+// d_w = dirs @ R^T, o = t broadcast).  Workgroup b takes rays [b * RB_RAYS, (b + 1) * RB_RAYS): the grid depends on N
+// alone.  Each thread adds its rays' 12 products in double (a product of two floats is exact there), the workgroup
+// adds its threads in a fixed order (shuffle tree per wave, then the four waves in order) and writes 12 doubles;
+// rays_bwd_reduce_kernel adds the workgroups' partials in workgroup order.  No atomics: bitwise reproducible.
+constexpr int RB_PER_THREAD = 4, RB_RAYS = 256 * RB_PER_THREAD;
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(256) rays_from_dirs_bwd_kernel(const float* __restrict__ dirs, int64_t N, Mat34 c,
+                                                                 const float* __restrict__ g_rays,
+                                                                 float* __restrict__ g_dirs,
+                                                                 double* __restrict__ partial) {
+    __shared__ double red[4][12];
+    double acc[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) acc[e] = 0.0;
+#pragma unroll
+    for (int k = 0; k < RB_PER_THREAD; ++k) {
+        const int64_t p = (int64_t)blockIdx.x * RB_RAYS + k * 256 + threadIdx.x;
+        if (p < N) {
+            const float d[3] = {dirs[3 * p], dirs[3 * p + 1], dirs[3 * p + 2]};
+            const float* g = g_rays + 8 * p;   // columns 6:8 (near, far) are constants of a pose step: not read
+            const float go[3] = {g[0], g[1], g[2]}, gd[3] = {g[3], g[4], g[5]};
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc[4 * i + j] += (double)gd[i] * (double)d[j];
+                acc[4 * i + 3] += (double)go[i];
+            }
+            if (g_dirs) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    g_dirs[3 * p + j] = fmaf(c.m[8 + j], gd[2], fmaf(c.m[4 + j], gd[1], c.m[j] * gd[0]));
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+        const double s = wave_sum(acc[e]);
+        if (lane == 0) red[w][e] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        const int e = threadIdx.x;
+        partial[(int64_t)blockIdx.x * 12 + e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+    }
+}
+
+// one wave per element of g_c2w: lane l adds the partials of workgroups l, l + 64, ... in order, then the
+// shuffle tree; nblk = 0 writes zeros
+__global__ void __launch_bounds__(768) rays_bwd_reduce_kernel(const double* __restrict__ partial, int64_t nblk,
+                                                              float* __restrict__ g_c2w) {
+    const int lane = threadIdx.x & 63, e = threadIdx.x >> 6;
+    double s = 0.0;
+    for (int64_t b = lane; b < nblk; b += 64) s += partial[b * 12 + e];
+    s = wave_sum(s);
+    if (lane == 0) g_c2w[e] = (float)s;
+}
+
 __global__ void __launch_bounds__(256) ray_aabb_kernel(const float* __restrict__ o, const float* __restrict__ d, int64_t N,
                                                        Box box, float eps, float max_bound, float invalid_value,
                                                        float* __restrict__ tmin, float* __restrict__ tmax) {
@@ -165,6 +230,36 @@ extern "C" int acn_rays_from_dirs(const float* dirs, int64_t N, const float* c2w
     hipLaunchKernelGGL(rays_from_dirs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dirs,
                        N, c, aabb != nullptr, b, near_c, far_c, eps, max_bound, invalid_value, rays);
     return acn_check_launch("acn_rays_from_dirs");
+}
+
+extern "C" size_t acn_rays_from_dirs_bwd_workspace_bytes(int64_t N) {
+    const int64_t nblk = N > 0 ? (N + RB_RAYS - 1) / RB_RAYS : 0;
+    return (size_t)(nblk > 0 ? nblk : 1) * 12 * sizeof(double);
+}
+
+extern "C" int acn_rays_from_dirs_bwd(const float* dirs, int64_t N, const float* c2w, const float* g_rays, float* g_c2w,
+                                      float* g_dirs, void* workspace, size_t workspace_bytes, void* stream) {
+    ACN_REQUIRE(N >= 0 && c2w, "acn_rays_from_dirs_bwd: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    if (N == 0) {   // no rays: a zero pose gradient, nothing else to write
+        if (g_c2w) {
+            hipLaunchKernelGGL(rays_bwd_reduce_kernel, dim3(1), dim3(768), 0, s, (const double*)nullptr, (int64_t)0, g_c2w);
+            return acn_check_launch("acn_rays_from_dirs_bwd");
+        }
+        return ACN_OK;
+    }
+    ACN_REQUIRE(dirs && g_rays && g_c2w && workspace, "acn_rays_from_dirs_bwd: NULL pointer");
+    ACN_REQUIRE(workspace_bytes >= acn_rays_from_dirs_bwd_workspace_bytes(N),
+                "acn_rays_from_dirs_bwd: workspace of %zu bytes, %zu needed", workspace_bytes,
+                acn_rays_from_dirs_bwd_workspace_bytes(N));
+    ACN_REQUIRE((((uintptr_t)workspace) & 7) == 0, "acn_rays_from_dirs_bwd: workspace must be 8-byte aligned");
+    Mat34 c;
+    for (int i = 0; i < 12; ++i) c.m[i] = c2w[i];
+    const int64_t nblk = (N + RB_RAYS - 1) / RB_RAYS;
+    hipLaunchKernelGGL(rays_from_dirs_bwd_kernel, dim3((unsigned)nblk), dim3(256), 0, s, dirs, N, c, g_rays, g_dirs,
+                       (double*)workspace);
+    hipLaunchKernelGGL(rays_bwd_reduce_kernel, dim3(1), dim3(768), 0, s, (const double*)workspace, nblk, g_c2w);
+    return acn_check_launch("acn_rays_from_dirs_bwd");
 }
 
 extern "C" int acn_ray_aabb(const float* origins, const float* dirs, int64_t N, const float* aabb, float eps,

@@ -226,11 +226,16 @@ class MetaNGP(MetaModule):
         geo = self.geo_head(h, params=self.get_subdict(params, "geo_head"))
         return {"sigma": sigma, "geo_feat": geo}
 
-    def _fused_train_ok(self, x: Tensor) -> bool:
+    def _fused_train_ok(self, x: Tensor, params=None) -> bool:
         from .ray_rendering import _second_order
-        # _FusedMLPFn has no gradient for the SH features: differentiated inputs take the composed chain
-        return (x.is_cuda and self._fusable and x.dtype == torch.float32 and not _second_order()
-                and not wants_grad(x))
+        if not (x.is_cuda and self._fusable and x.dtype == torch.float32 and not _second_order()):
+            return False
+        if not wants_grad(x):
+            return True
+        # differentiated inputs: _FusedMLPFn returns dL/dh0 and dL/dsh in one launch when the MLP is frozen (pose
+        # refinement, localisation); with a trainable MLP tensor, or under AMP, they take the composed chain
+        return (_FusedMLPFn.INPUT_GRAD_FUSED and ops.TRAIN_MLP_PRECISION != "amp"
+                and not wants_grad(*self._mlp_tensors(params).values()))
 
     def forward(self, x_d: Tensor, params=None) -> Tensor:
         """[xyz(3), dir(3)] -> [rgb(3), sigma(1)] (meta_ngp.py:226-241)."""
@@ -244,12 +249,15 @@ class MetaNGP(MetaModule):
             return ops.field_fwd(flat, [spec], r, active_module=0,
                                  packed=self.packed_weights(spec, r, params)).view(*x_d.shape[:-1], 4)
         x, d = x_d[..., :3], x_d[..., 3:6]
-        if self._fused_train_ok(x_d):
-            # training: hash grid (HIP, autograd to the table) + the whole MLP fwd/bwd on MFMA
+        if self._fused_train_ok(x_d, params):
+            # training: hash grid (HIP, autograd to the table and the points) + the whole MLP fwd/bwd on MFMA
             flat = x_d.reshape(-1, 6)
             h0 = self._enc_xyz(flat[:, :3])
-            with torch.no_grad():
-                sh = self._enc_dir(flat[:, 3:6])
+            if wants_grad(x_d):
+                sh = self._enc_dir(flat[:, 3:6])   # _SHFn: the gradient reaches the directions
+            else:
+                with torch.no_grad():
+                    sh = self._enc_dir(flat[:, 3:6])
             ws = [t.contiguous() for t in self._mlp_tensors(params).values()]
             out = _FusedMLPFn.apply(h0.contiguous(), sh.contiguous(), *ws)
             return out.view(*x_d.shape[:-1], 4)
@@ -380,20 +388,32 @@ class _FusedMLPFn(torch.autograd.Function):
     backward -> one fused kernel (acn_mlp_train_bwd_dw) that re-runs the forward of each 32-sample tile in
     registers and returns dL/d(hash features) and all 14 [dW | db] (no per-sample activations are saved).
     With DW_FUSED off, the previous split path: the forward saves the layer inputs feature-major and each
-    layer's [dW | db] is one batched GEMM dY^T . [X | 1] over the batch.  First-order only: second-order
-    MAML renders inside ray_rendering.second_order(), which keeps the composed torch chain."""
+    layer's [dW | db] is one batched GEMM dY^T . [X | 1] over the batch.  When no weight needs a gradient
+    (frozen MLP: pose refinement, or only the table trains) the backward is one acn_mlp_train_bwd_input launch
+    instead, which returns dL/d(hash features) -- bit-identical to the fused backward's -- and dL/d(SH features)
+    and forms no weight gradient; INPUT_GRAD_FUSED off restores the previous behaviour (no SH gradient: MetaNGP
+    then composes the torch chain for differentiated inputs).  First-order only: second-order MAML renders
+    inside ray_rendering.second_order(), which keeps the composed torch chain."""
 
     DW_FUSED = True
+    INPUT_GRAD_FUSED = True   # tests and tools/bench_pose_grad.py switch it off to compare with the composed chain
 
     @staticmethod
     def forward(ctx, h0, sh, *ws):
         need = any(ctx.needs_input_grad)
-        fused = _FusedMLPFn.DW_FUSED
+        wgrad = any(ctx.needs_input_grad[2:])
+        prec = ops.TRAIN_MLP_PRECISION
+        inputs_only = need and not wgrad and _FusedMLPFn.INPUT_GRAD_FUSED and prec != "amp"
+        if ctx.needs_input_grad[1] and not inputs_only:
+            raise ops.AcnError("the fused MLP returns a gradient for the SH features only with frozen weights "
+                               "(INPUT_GRAD_FUSED, precision fp16x3 / fp32); MetaNGP.forward composes the torch "
+                               "chain otherwise")
+        fused = _FusedMLPFn.DW_FUSED or inputs_only
         # the forward's packed weight image is kept for the fused backward (same weights: autograd's saved-
         # tensor version check rejects an in-place change in between), which then packs nothing itself
-        prec = ops.TRAIN_MLP_PRECISION
         out, save, img = ops.mlp_train_fwd(h0, sh, ws, save=need and not fused, precision=prec, return_img=True)
         ctx.fused = fused
+        ctx.inputs_only = inputs_only
         ctx.prec = prec
         ctx.img = img if need and fused else None
         if need:
@@ -405,7 +425,16 @@ class _FusedMLPFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            from .encodings import _first_order_only
+            _first_order_only("MetaNGP MLP")   # dL/dh0, dL/dsh come from kernels autograd cannot differentiate
         need = ctx.needs_input_grad[2:]
+        if ctx.inputs_only:
+            h0, sh, out, *ws = ctx.saved_tensors
+            gh, gsh = ops.mlp_train_bwd_input(h0, sh, out, g.contiguous(), ws, want_h0=ctx.needs_input_grad[0],
+                                              want_sh=ctx.needs_input_grad[1], img=ctx.img, precision=ctx.prec)
+            ctx.img = None
+            return (gh, gsh, *[None] * len(need))
         if ctx.fused:
             h0, sh, out, *ws = ctx.saved_tensors
             grads, gh = ops.mlp_train_bwd_dw(h0, sh, out, g.contiguous(), ws, want_h0=ctx.needs_input_grad[0],

@@ -448,6 +448,27 @@ def rays_from_dirs(dirs: torch.Tensor, c2w: torch.Tensor, aabb: Optional[torch.T
     return rays
 
 
+def rays_from_dirs_bwd(dirs: torch.Tensor, c2w: torch.Tensor, g_rays: torch.Tensor, want_dirs: bool = True):
+    """Backward of rays_from_dirs in the pose and the directions (acn_rays_from_dirs_bwd): g_c2w (3,4) fp32 on the
+    rays' device and g_dirs (N,3) fp32 (None without ``want_dirs``) from dL/drays (N,8).  Columns 6:8 of g_rays
+    (near, far) are ignored: the t-values are constants of a pose step.  Deterministic (double partial sums added
+    in a fixed order, no atomics)."""
+    require_hip(dirs, "get_rays")
+    d = _f32(dirs).view(-1, 3)
+    g = _f32(g_rays).view(-1, 8)
+    N = d.shape[0]
+    if g.shape[0] != N:
+        raise AcnError(f"g_rays must be ({N}, 8), got {tuple(g.shape)}")
+    c = _host_f32(c2w[:3, :4], 12)
+    g_c2w = torch.empty(3, 4, device=d.device, dtype=torch.float32)
+    g_dirs = torch.empty(N, 3, device=d.device, dtype=torch.float32) if want_dirs else None
+    L = _lib.lib()
+    ws = torch.empty(int(L.acn_rays_from_dirs_bwd_workspace_bytes(N)) // 8, dtype=torch.float64, device=d.device)
+    check(L.acn_rays_from_dirs_bwd(ptr(d), N, c, ptr(g), ptr(g_c2w), ptr(g_dirs), ptr(ws), ws.numel() * 8,
+                                   stream_of(d)), "acn_rays_from_dirs_bwd")
+    return g_c2w, g_dirs
+
+
 def ray_aabb(origins: torch.Tensor, dirs: torch.Tensor, aabb: torch.Tensor, eps: float, max_bound: float,
              invalid_value: float):
     require_hip(origins, "SceneBox.ray_aabb_intersect")
@@ -665,6 +686,40 @@ def mlp_train_bwd_dw(h0: torch.Tensor, sh: torch.Tensor, out: torch.Tensor, gout
         grads.append(dw[o:o + n].view(shp))
         o += n
     return grads, gh
+
+
+def mlp_train_bwd_input(h0: torch.Tensor, sh: torch.Tensor, out: torch.Tensor, gout: torch.Tensor,
+                        ws: Sequence[torch.Tensor], want_h0: bool = True, want_sh: bool = True,
+                        img: Optional[torch.Tensor] = None, precision: Optional[str] = None):
+    """Input gradients of the expert MLP with frozen weights (acn_mlp_train_bwd_input): (dL/dh0 (M,32) or None,
+    dL/dsh (M,16) or None) from h0 / sh (the forward is re-run in registers) and dL/dout.  One launch, no weight
+    gradients; gh0 is bit-identical to mlp_train_bwd_dw's, every row depends on its own sample only.  ``img``: the
+    packed image mlp_train_fwd(return_img=True) returned for the same weights and precision.  "amp" is not
+    exposed (differentiated inputs keep the composed chain under AMP)."""
+    require_hip(h0, "MetaNGP MLP (input gradients)")
+    precision = precision or TRAIN_MLP_PRECISION
+    if precision == "amp":
+        raise AcnError("mlp_train_bwd_input: precision 'amp' is not supported (fp16x3 or fp32)")
+    M = out.shape[0]
+    if h0.shape != (M, 32) or sh.shape != (M, 16) or gout.shape != (M, 4):
+        raise AcnError(f"mlp_train_bwd_input: h0 (M,32), sh (M,16), out / gout (M,4) expected, got "
+                       f"{tuple(h0.shape)}, {tuple(sh.shape)}, {tuple(out.shape)}, {tuple(gout.shape)}")
+    for name, t in (("h0", h0), ("sh", sh), ("out", out), ("gout", gout)):
+        if not (t.is_contiguous() and t.dtype == torch.float32):
+            raise AcnError(f"mlp_train_bwd_input: {name} must be a contiguous fp32 tensor")
+    gh = torch.empty(M, 32, device=out.device, dtype=torch.float32) if want_h0 else None
+    gs = torch.empty(M, 16, device=out.device, dtype=torch.float32) if want_sh else None
+    if img is not None:
+        check(mlp_fn("acn_mlp_train_bwd_input_img", precision)(ptr(h0), ptr(sh), ptr(out), ptr(gout), M, ptr(img),
+                                                                ptr(gh), ptr(gs), stream_of(out)),
+              "acn_mlp_train_bwd_input_img")
+    else:
+        w = _mlp_struct(ws)
+        wsp = torch.empty(int(mlp_fn("acn_mlp_workspace_bytes", precision)()), dtype=torch.uint8, device=out.device)
+        check(mlp_fn("acn_mlp_train_bwd_input", precision)(ptr(h0), ptr(sh), ptr(out), ptr(gout), M, C.byref(w),
+                                                            ptr(gh), ptr(gs), ptr(wsp), stream_of(out)),
+              "acn_mlp_train_bwd_input")
+    return gh, gs
 
 
 def sample_stratified(rays: torch.Tensor, S: int, jitter: Optional[torch.Tensor], aabb_min, aabb_extent,

@@ -10,14 +10,57 @@ from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
 from . import ops
+from .encodings import _first_order_only, wants_grad
 from .scene_box import SceneBox
+
+
+class _RaysFromDirsFn(torch.autograd.Function):
+    """ops.rays_from_dirs under autograd: the forward is the same kernel call (identical values); the backward is
+    acn_rays_from_dirs_bwd, the gradient of d_w = R . dir, o = t in the pose and the directions.  The near / far
+    columns carry no gradient (the t-values are constants of a pose step, as for differentiable rays).  First
+    order only.  Gradients come back in the shape, dtype and device of ``c2w`` and ``directions``; the last row
+    of a 4x4 pose gets zeros."""
+
+    @staticmethod
+    def forward(ctx, directions, c2w, aabb, near_c, far_c, eps, max_bound, invalid_value):
+        ctx.save_for_backward(directions, c2w)
+        return ops.rays_from_dirs(directions, c2w, aabb, near_c=near_c, far_c=far_c, eps=eps, max_bound=max_bound,
+                                  invalid_value=invalid_value)
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("get_rays")
+        return _RaysFromDirsFn._backward(ctx, g)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, g):
+        directions, c2w = ctx.saved_tensors
+        want_c, want_d = ctx.needs_input_grad[1], ctx.needs_input_grad[0]
+        g_c2w, g_dirs = ops.rays_from_dirs_bwd(directions, c2w, g, want_dirs=want_d)
+        gc = None
+        if want_c:
+            gc = torch.zeros(c2w.shape, dtype=torch.float32, device=g_c2w.device)
+            gc[:3, :4] = g_c2w
+            gc = gc.to(device=c2w.device, dtype=c2w.dtype)
+        gd = g_dirs.view(directions.shape).to(directions.dtype) if want_d else None
+        return gd, gc, None, None, None, None, None, None
+
+
+def _rays_from_dirs(directions: Tensor, c2w: Tensor, aabb, **kw) -> Tensor:
+    """(N,8) rays; through autograd when the pose or the directions require grad, else exactly ops.rays_from_dirs."""
+    if wants_grad(c2w, directions):
+        return _RaysFromDirsFn.apply(directions, c2w, aabb, kw.get("near_c", 0.0), kw.get("far_c", 0.0),
+                                     kw.get("eps", 1e-8), kw.get("max_bound", 1e10), kw.get("invalid_value", 1e10))
+    return ops.rays_from_dirs(directions, c2w, aabb, **kw)
 
 
 def _rays_cam_to_world(dirs_cam: Tensor, c2w: Tensor) -> Tuple[Tensor, Tensor]:
     """Camera-frame directions -> world-frame origins & directions (ray_sampling.py:10-24)."""
-    rays = ops.rays_from_dirs(dirs_cam, c2w, None)
+    rays = _rays_from_dirs(dirs_cam, c2w, None)
     shape = dirs_cam.shape
     return rays[:, :3].reshape(*shape), rays[:, 3:6].reshape(*shape)
 
@@ -34,7 +77,9 @@ def unpack_rays(rays: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
 
 def get_rays(directions: Tensor, c2w: Tensor, scene_box: Optional[SceneBox] = None, near: Optional[float] = None,
              far: Optional[float] = None, *, aabb_max_bound: float = 1e10, aabb_invalid_value: float = 1e10) -> Tensor:
-    """(H,W,3) -> (H,W,8) or (N,3) -> (N,8) rays [o, d, near, far] (ray_sampling.py:50-108)."""
+    """(H,W,3) -> (H,W,8) or (N,3) -> (N,8) rays [o, d, near, far] (ray_sampling.py:50-108).  A ``c2w`` or
+    ``directions`` that requires grad receives its gradient (pose refinement): first order, and none through the
+    near / far columns."""
     if directions.ndim == 2 and directions.shape[1] == 3:
         out_shape = (directions.shape[0], 8)
     elif directions.ndim == 3 and directions.shape[-1] == 3:
@@ -43,9 +88,9 @@ def get_rays(directions: Tensor, c2w: Tensor, scene_box: Optional[SceneBox] = No
         raise ValueError(f"directions must be (H, W, 3) or (N, 3), got {tuple(directions.shape)}")
     if scene_box is None and (near is None or far is None):
         raise ValueError("Provide near/far when scene_box is None")
-    rays = ops.rays_from_dirs(directions, c2w, None if scene_box is None else scene_box.aabb,
-                              near_c=float(near or 0.0), far_c=float(far or 0.0), eps=1e-8,
-                              max_bound=aabb_max_bound, invalid_value=aabb_invalid_value)
+    rays = _rays_from_dirs(directions, c2w, None if scene_box is None else scene_box.aabb,
+                           near_c=float(near or 0.0), far_c=float(far or 0.0), eps=1e-8,
+                           max_bound=aabb_max_bound, invalid_value=aabb_invalid_value)
     return rays.view(*out_shape)
 
 

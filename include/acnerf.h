@@ -214,6 +214,21 @@ int acn_rays_from_dirs(const float* dirs, int64_t N, const float* c2w, const flo
                        float far_c, float eps, float max_bound, float invalid_value, float* rays,
                        void* stream);
 
+/* Backward of acn_rays_from_dirs in the pose and the directions (_rays_cam_to_world, ray_sampling.py:10-24:
+ * d_w = dirs @ R^T, o = t; no normalisation).  dirs (N,3) device, c2w host (3,4), g_rays (N,8) device = dL/drays;
+ *   g_c2w (12 floats, device, row-major 3x4, overwritten): g_c2w[i][j<3] = sum_n g_rays[n,3+i] * dirs[n,j],
+ *                                                          g_c2w[i][3]   = sum_n g_rays[n,i];
+ *   g_dirs (N,3) device or NULL:                           g_dirs[n,j]   = sum_i R[i][j] * g_rays[n,3+i].
+ * Columns 6:8 of g_rays (near, far) are ignored: stratified_t_vals is a no-grad function here and in the
+ * reference, so the t-values -- and with them the slab test's near / far -- are constants of a pose step (the
+ * rule DESIGN.md 4o takes for rays).  Deterministic: per-thread and per-workgroup sums in double, a grid fixed by
+ * N alone, the workgroups' partials (in the workspace) added in workgroup order by a second launch; no atomics.
+ * N == 0 writes zeros to g_c2w (when it is not NULL).  workspace: acn_rays_from_dirs_bwd_workspace_bytes(N)
+ * device bytes, 8-byte aligned.                                                                  */
+size_t acn_rays_from_dirs_bwd_workspace_bytes(int64_t N);
+int acn_rays_from_dirs_bwd(const float* dirs, int64_t N, const float* c2w, const float* g_rays, float* g_c2w,
+                           float* g_dirs, void* workspace, size_t workspace_bytes, void* stream);
+
 /* SceneBox.ray_aabb_intersect (nerfs/scene_box.py:45-107): origins, dirs (N,3) -> tmin, tmax (N). */
 int acn_ray_aabb(const float* origins, const float* dirs, int64_t N, const float* aabb, float eps,
                  float max_bound, float invalid_value, float* tmin, float* tmax, void* stream);
@@ -474,6 +489,19 @@ int acn_mlp_train_bwd_dw(const float* h0, const float* sh, const float* out, con
  * own pack launch).  The weights must not have changed since that forward.                          */
 int acn_mlp_train_bwd_dw_img(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
                              const float* img, float* dw, float* gh0, void* workspace, void* stream);
+/* Input gradients with frozen weights: dL/dh0 and dL/dsh of the forward (MetaNGP.forward's MLP, models/inr/
+ * meta_ngp.py:171-241: sigma trunk, heads, torch.cat([geo_feat, d_enc]) of :207-211, colour MLP, sigmoid /
+ * trunc_exp) from dL/dout (M, 4); out = the forward's output.  One kernel re-runs the forward of each 32-sample
+ * tile in registers (bit for bit the forward's activations) and the dX chain of acn_mlp_train_bwd_dw without its
+ * [dW | db] half; gh0 (M, 32) is bit-identical to that call's, gsh (M, 16) = rows 15..30 of d(colour input).
+ * Both are overwritten; either may be NULL (skipped); both NULL or M == 0 is a no-op.  No atomics, no partial
+ * sums: every row depends on its own sample only, so results repeat bit for bit and do not depend on M.
+ * workspace: acn_mlp_workspace_bytes() device bytes (the packed image).  _img: on the image acn_mlp_train_fwd
+ * packed into its workspace for the same, unchanged weights (no pack launch, no workspace).          */
+int acn_mlp_train_bwd_input(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
+                            const acn_mlp* w, float* gh0, float* gsh, void* workspace, void* stream);
+int acn_mlp_train_bwd_input_img(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
+                                const float* img, float* gh0, float* gsh, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Episodic task routing (data.hip).  Replaces TaskDataset's region clip + micro-cell assignment
@@ -702,7 +730,7 @@ int acn_mse_linear_bwd(const float* pred, const float* gt, int64_t n, const floa
 
 
 /* The training MLP in exact fp32 (v_mfma_f32_32x32x2_f32 layer products instead of the fp32-accurate fp16x3
- * split): the same ten entry points, suffixed _exact, same arguments and semantics; workspaces must come
+ * split): the same twelve entry points, suffixed _exact, same arguments and semantics; workspaces must come
  * from the _exact size functions (the weight image layout differs).  mlp_train.hip compiled a second time
  * with -DACN_TRAIN_F16X3=0 (a runtime precision switch for parity studies: DESIGN.md 4). */
 size_t acn_mlp_workspace_bytes_exact(void);
@@ -715,6 +743,10 @@ int acn_mlp_train_bwd_dw_exact(const float* h0, const float* sh, const float* ou
                          const acn_mlp* w, float* dw, float* gh0, void* workspace, void* stream);
 int acn_mlp_train_bwd_dw_img_exact(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
                              const float* img, float* dw, float* gh0, void* workspace, void* stream);
+int acn_mlp_train_bwd_input_exact(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
+                            const acn_mlp* w, float* gh0, float* gsh, void* workspace, void* stream);
+int acn_mlp_train_bwd_input_img_exact(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
+                                const float* img, float* gh0, float* gsh, void* stream);
 size_t acn_mlp_pairs_workspace_bytes_exact(int K);
 int acn_mlp_pack_pairs_exact(const acn_mlp* const* w, int K, void* workspace, void* stream);
 int acn_mlp_train_fwd_pairs_exact(const float* h0, const float* sh, const int64_t* seg, int K, const void* workspace,
@@ -726,7 +758,7 @@ int acn_mlp_train_bwd_dw_pairs_exact(const float* h0, const float* sh, const flo
  * pipelines/online_stage/runtime_adapt.py:249-259, pipelines/offline_stage/meta_core.py:38, configs/train.json:37):
  * one fp16 x fp16 MFMA product per term with fp32 accumulation, every layer output, activation, dX and
  * [dW | db] rounded to fp16 once, the incoming gradient cast to fp16; no internal rescaling (the caller's
- * loss scale -- acn_amp_unscale_coef -- keeps the gradients in fp16's range, as GradScaler does).  The same ten
+ * loss scale -- acn_amp_unscale_coef -- keeps the gradients in fp16's range, as GradScaler does).  The same twelve
  * entry points, suffixed _amp; workspaces from the _amp size functions.  mlp_train.hip compiled a third
  * time with -DACN_TRAIN_AMP=1. */
 size_t acn_mlp_workspace_bytes_amp(void);
@@ -739,6 +771,10 @@ int acn_mlp_train_bwd_dw_amp(const float* h0, const float* sh, const float* out,
                              const acn_mlp* w, float* dw, float* gh0, void* workspace, void* stream);
 int acn_mlp_train_bwd_dw_img_amp(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
                                  const float* img, float* dw, float* gh0, void* workspace, void* stream);
+int acn_mlp_train_bwd_input_amp(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
+                            const acn_mlp* w, float* gh0, float* gsh, void* workspace, void* stream);
+int acn_mlp_train_bwd_input_img_amp(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
+                                const float* img, float* gh0, float* gsh, void* stream);
 size_t acn_mlp_pairs_workspace_bytes_amp(int K);
 int acn_mlp_pack_pairs_amp(const acn_mlp* const* w, int K, void* workspace, void* stream);
 int acn_mlp_train_fwd_pairs_amp(const float* h0, const float* sh, const int64_t* seg, int K, const void* workspace,
