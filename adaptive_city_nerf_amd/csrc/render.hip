@@ -16,8 +16,10 @@
 // across tiles, and stops the ray once T < tau (early ray termination; tau = 0 disables it).
 //
 // The render kernels and when acn_render_stratified_fwd_ordered / acn_render_packed_fwd launch each:
-//   render_ws_kernel     one expert, S <= 256, tau <= 0: a workgroup's 16 rays cut into depth tiles
-//   render_kernel        one expert otherwise, and routed K == 2 (both images in LDS): one wave per ray
+//   render_ws_kernel     one expert, S <= 256, tau <= 0: a workgroup's 16 rays cut into depth tiles; the C2 call is
+//                        this kernel alone -- it derives the visiting order of a small batch in its prologue
+//   render_kernel        one expert otherwise, and routed K == 2 (both images in LDS): one wave per ray, after
+//                        ray_order_kernel for a small batch
 //   render_wss_kernel    routed K > 2, S <= 256, tau <= 0: depth tiles over two LDS expert slots
 //                        (16-ray rounds up to S = 128, else 8-ray rounds)
 //   render_slots_kernel  routed K > 2 otherwise: one wave per ray over two LDS expert slots
@@ -33,6 +35,7 @@
 //   ACN_HASH_DEPTH, ACN_SLOTS_THREADS  plain constants
 #include "acn_device.h"
 #include "acn_internal.h"
+#include "ray_order.h"
 
 using namespace acn;
 
@@ -864,6 +867,7 @@ struct RenderParams {
     const int32_t* order;  // optional visiting order (ray_order_kernel); NULL = rays in the given order
     const int32_t* norder; // render_slots_kernel: device count of `order` entries (the multi-expert rays of the
                            // split routed render); NULL = N
+    int32_t ws_select;     // render_ws_kernel: derive the visiting order in the kernel (ws_select_*, ray_order.h)
 };
 
 // t of sample i without jitter, branch-free (same roundings as lin01/tlin)
@@ -1065,21 +1069,49 @@ __device__ __forceinline__ void composite_ray_lds(const RenderParams& p, const B
     finish_and_store(acc, bg, r.dx, r.dy, r.dz, lane, ray, p);
 }
 
+// The visiting order (p.ws_select): the workgroup derives the rays of its own rounds in a prologue (ws_select_*,
+// ray_order.h) beside the weight staging, in LDS that aliases ybuf, instead of reading an order[] that a kernel
+// of its own wrote first.  The rounds' slot table (kSelRounds x 16 ray indices, 16 bit) lives in the padding at
+// the end of the packed image's LDS copy, which nothing reads.
+constexpr bool kWsExactFrame = true;    // the prologue's frame: 256 sampled rays per wave (false) or ray_order_kernel's
+                                        // two workgroup reductions over all rays (true); DESIGN.md §4 has the A/B
+constexpr int kWsTabOff = PK_BC3 + 4;
+static_assert((PK_FLOATS - kWsTabOff) * 2 >= kSelRounds * 16, "slot table: the packed image's padding holds it");
+static_assert(sizeof(SelLds) <= 16 * kWsMaxS * sizeof(f32x4), "selection scratch aliases ybuf");
+
 template <int INTERP>
 __global__ void __launch_bounds__(1024, 4) render_ws_kernel(FieldCfg cfg, BgArgs bg, RenderParams p) {
     __shared__ __attribute__((aligned(16))) float smem[PK_FLOATS];
     __shared__ __attribute__((aligned(16))) float cbuf[16 * 64];   // the round rays' folded colour biases
     __shared__ __attribute__((aligned(16))) f32x4 ybuf[16 * kWsMaxS];
     __shared__ int qhead;
-    stage_weights<1>(smem, p.packed);
+    const uint16_t* tab = reinterpret_cast<const uint16_t*>(smem + kWsTabOff);
+    // the rays of a round: 16 consecutive positions, XCD bands as in render_kernel
+    int64_t base, hi, stride;
+    xcd_band(p.N, 16, base, hi, stride);
+    if (p.ws_select) {   // the direction loads fly while the weights are staged
+        SelLds& sel = *reinterpret_cast<SelLds*>(ybuf);
+        SelRays sr;
+        ws_select_begin<kWsExactFrame>(p.rays, (int)p.N, sr, sel);
+        stage_weights<1>(smem, p.packed);
+        ws_select_finish<kWsExactFrame>(sr, (int)p.N, (int)base, (int)hi, (int)stride, sel,
+                                        reinterpret_cast<uint16_t*>(smem + kWsTabOff));
+    } else {
+        stage_weights<1>(smem, p.packed);
+    }
     const float* W = smem;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int S = p.S;
     const float step = 1.0f / (float)(S - 1);
-    // the rays of a round: 16 consecutive positions, XCD bands as in render_kernel
-    int64_t base, hi, stride;
-    xcd_band(p.N, 16, base, hi, stride);
-    for (; base < hi; base += stride) {   // block-uniform
+    // position base + ls of the order: the ray in slot ls of round k
+    auto ray_at = [&](int k, int64_t base, int ls) -> int64_t {
+        return p.ws_select ? (int64_t)tab[k * 16 + ls] : p.order ? (int64_t)p.order[base + ls] : base + ls;
+    };
+    auto ray_of_wave = [&](int k, int64_t base) -> int64_t {   // ... and of slot `wave`, wave-uniform
+        if (p.ws_select) return (int64_t)__builtin_amdgcn_readfirstlane((int)tab[k * 16 + wave]);
+        return p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[base + wave]) : base + wave;
+    };
+    for (int k = 0; base < hi; base += stride, ++k) {   // block-uniform
         // the lane index re-derived per round through an opaque copy: the per-lane LDS addresses and constants
         // formed from it stay inside the loop instead of being hoisted into registers held across it (spilled)
         const int tid = opaque_v((int)threadIdx.x);
@@ -1089,7 +1121,7 @@ __global__ void __launch_bounds__(1024, 4) render_ws_kernel(FieldCfg cfg, BgArgs
         if (tid == 0) qhead = 0;
         if (wave < nr) {
             // wave w folds round slot w's colour bias into cbuf[w] once; every tile of that ray reads it there
-            const int64_t r0 = p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[base + wave]) : base + wave;
+            const int64_t r0 = ray_of_wave(k, base);
             const float* rp = p.rays + r0 * 8;
             float sh[16], sv[8];
             dir_sh(rp[3], rp[4], rp[5], sh, kz);
@@ -1115,7 +1147,7 @@ __global__ void __launch_bounds__(1024, 4) render_ws_kernel(FieldCfg cfg, BgArgs
             if (g != gcur) {   // wave-uniform
                 slot = g * R + (j % R);
                 const int ls = slot < nr ? slot : nr - 1;
-                r = load_ray(p, p.order ? (int64_t)p.order[base + ls] : base + ls);
+                r = load_ray(p, ray_at(k, base, ls));
                 gcur = g;
             }
             const int s = q * D + j / R;
@@ -1133,7 +1165,7 @@ __global__ void __launch_bounds__(1024, 4) render_ws_kernel(FieldCfg cfg, BgArgs
         }
         __syncthreads();   // every sample of the round's rays is in ybuf
         if (wave < nr) {
-            const int64_t ray_w = p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[base + wave]) : base + wave;
+            const int64_t ray_w = ray_of_wave(k, base);
             composite_ray_lds(p, bg, ray_w, ybuf + wave * kWsMaxS, lane, step);
         }
         __syncthreads();   // ybuf / qhead reused by the next round
@@ -1518,15 +1550,6 @@ __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) re
 
 // inclusive scan over the 64 lanes of a wave on DPP: row_shr 1/2/4/8 inside each 16-lane row, then
 // row_bcast:15 / :31 carry the row totals upward (gfx9-family DPP)
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
-    return v;
-}
 // lanes of this wave (among `valid`) holding the same 6-bit digit, and how many of them sit below this lane
 __device__ __forceinline__ uint64_t same_digit_lanes(bool valid, int dig) {
     uint64_t m = __ballot(valid);
@@ -2216,66 +2239,10 @@ __global__ void __launch_bounds__(256) sample_train_kernel(const float* __restri
     for (int q = 0; q < 4; ++q) o4[q] = make_float4(sh[4 * q], sh[4 * q + 1], sh[4 * q + 2], sh[4 * q + 3]);
 }
 
-// Visiting order of a small batch (N <= ACN_ORDER_MAX): rays grouped by direction, so that the XCD
-// bands of render_kernel become compact image regions (a random pixel batch otherwise spreads every
-// XCD's samples over the whole frame and its 4 MB L2 serves the hash cells of all of it).  One
-// workgroup: the batch's mean direction m and an orthonormal pair (e1, e2) perpendicular to it; every
-// ray's gnomonic coordinates (d.e1 / d.m, d.e2 / d.m) (for one camera: its image-plane position),
-// quantised to a 64 x 64 grid over the batch's bounding box and Z-ordered; a STABLE sort of the rays by
-// cell (two 6-bit LSD radix passes, rank inside a wave by ballot multisplit, so rays of one cell keep
-// their index order and the visiting order is reproducible run to run).
-// Only the order changes: each ray is still rendered alone and its outputs written at its own index,
-// so results are bit-identical to the given order.  Rays with a non-finite direction or d.m <= 0
-// go to the last cell.
-#define ACN_ORDER_MAX 8192
-#define ACN_ORDER_BINS 4096
-__device__ __forceinline__ uint32_t spread6(uint32_t v) {
-    v &= 63u;
-    v = (v | (v << 4)) & 0x30Fu;
-    v = (v | (v << 2)) & 0x333u;
-    v = (v | (v << 1)) & 0x555u;
-    return v;
-}
-// workgroup-wide reductions (1024 threads = 16 waves) of 3 sums / 4 maxima; every thread gets the result
-// DPP within each 16-lane row (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror), then the
-// four row results through scalar readlanes: no LDS round trips (a ds_bpermute shuffle ladder costs six
-// dependent LDS latencies per value)
-template <int OP>
-__device__ __forceinline__ float wave_reduce(float v) {
-    auto op = [](float a, float b) { return OP == 0 ? a + b : fmaxf(a, b); };
-    v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false)));
-    v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false)));
-    v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false)));
-    v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false)));
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return op(op(r0, r1), op(r2, r3));
-}
-template <int OP>
-__device__ __forceinline__ void block_reduce3(float& a, float& b, float& c, float* red) {
-    a = wave_reduce<OP>(a), b = wave_reduce<OP>(b), c = wave_reduce<OP>(c);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[w] = a, red[16 + w] = b, red[32 + w] = c;
-    __syncthreads();
-    a = red[0], b = red[16], c = red[32];
-    for (int k = 1; k < 16; ++k) a += red[k], b += red[16 + k], c += red[32 + k];
-    __syncthreads();  // red[] reuse
-}
-__device__ __forceinline__ void block_reduce4max(float& a, float& b, float& c, float& d, float* red) {
-    a = wave_reduce<1>(a), b = wave_reduce<1>(b), c = wave_reduce<1>(c), d = wave_reduce<1>(d);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[w] = a, red[16 + w] = b, red[32 + w] = c, red[48 + w] = d;
-    __syncthreads();
-    for (int k = 0; k < 16; ++k)
-        a = fmaxf(a, red[k]), b = fmaxf(b, red[16 + k]), c = fmaxf(c, red[32 + k]), d = fmaxf(d, red[48 + k]);
-    __syncthreads();
-}
-__device__ __forceinline__ bool dir_ok(float x, float y, float z) {
-    const float n2 = x * x + y * y + z * z;
-    return n2 > 0.0f && n2 < 3.0e38f;  // finite, non-zero
-}
+// ray_order_kernel: the visiting order of a small batch (ray_order.h), whole, by one workgroup -- a STABLE sort of
+// the rays by cell (a counting sort with per-cell ranks, or two 6-bit LSD radix passes with the rank inside a wave
+// by ballot multisplit), so rays of one cell keep their index order and the order is reproducible run to run.
+// render_ws_kernel derives its windows of this order itself (ws_select_*); the other render kernels read order[].
 // One stable LSD radix pass over N <= ACN_ORDER_MAX 16-bit keys by digit (key >> shift) & 63, 1024 threads.
 // Wave w owns the contiguous input block [w B, (w + 1) B); per (digit, wave) counts cnt[digit * 16 + w]
 // are scanned digit-major, so the output keeps every digit's elements in input order: within a wave
@@ -2345,34 +2312,11 @@ __global__ void __launch_bounds__(1024) ray_order_kernel(const float* __restrict
             const float* rp = rays + (int64_t)i * 8;
             const float x = rp[3], y = rp[4], z = rp[5];
             dir[0][i] = x, dir[1][i] = y, dir[2][i] = z;
-            if (dir_ok(x, y, z)) {
-                const float r = rsqrtf(x * x + y * y + z * z);
-                sx += x * r, sy += y * r, sz += z * r;
-            }
+            order_accum_dir(x, y, z, sx, sy, sz);
         }
     }
     block_reduce3<0>(sx, sy, sz, red);
-    const float mn = sqrtf(sx * sx + sy * sy + sz * sz);
-    float mx = 0.0f, my = 0.0f, mz = 1.0f;
-    if (mn > 0.0f && mn < 3.0e38f) mx = sx / mn, my = sy / mn, mz = sz / mn;
-    // e1 = normalize(m x a) with a the axis least aligned with m; e2 = m x e1
-    float ax = 0.0f, ay = 0.0f, az = 0.0f;
-    if (fabsf(mx) <= fabsf(my) && fabsf(mx) <= fabsf(mz)) ax = 1.0f;
-    else if (fabsf(my) <= fabsf(mz)) ay = 1.0f;
-    else az = 1.0f;
-    float e1x = my * az - mz * ay, e1y = mz * ax - mx * az, e1z = mx * ay - my * ax;
-    const float e1n = rsqrtf(e1x * e1x + e1y * e1y + e1z * e1z);
-    e1x *= e1n, e1y *= e1n, e1z *= e1n;
-    const float e2x = my * e1z - mz * e1y, e2y = mz * e1x - mx * e1z, e2z = mx * e1y - my * e1x;
-    auto coords = [&](int i, float& u, float& v) -> bool {
-        const float x = dir[0][i], y = dir[1][i], z = dir[2][i];
-        if (!dir_ok(x, y, z)) return false;
-        const float dm = x * mx + y * my + z * mz;
-        if (!(dm > 0.0f)) return false;
-        u = (x * e1x + y * e1y + z * e1z) / dm;
-        v = (x * e2x + y * e2y + z * e2z) / dm;
-        return fabsf(u) < 1.0e30f && fabsf(v) < 1.0e30f;
-    };
+    const OrderFrame f = order_frame(sx, sy, sz);
     float umin = 3.0e38f, vmin = 3.0e38f, umax = -3.0e38f, vmax = -3.0e38f;
     // each thread's (u, v) kept in registers for the cell pass below (one coordinate pass over dir[], not two)
     float cu[PER], cv[PER];
@@ -2380,25 +2324,20 @@ __global__ void __launch_bounds__(1024) ray_order_kernel(const float* __restrict
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const int i = tid + q * 1024;
-        cok[q] = i < N && coords(i, cu[q], cv[q]);
-        if (cok[q]) umin = fminf(umin, cu[q]), umax = fmaxf(umax, cu[q]), vmin = fminf(vmin, cv[q]), vmax = fmaxf(vmax, cv[q]);
+        cok[q] = false, cu[q] = cv[q] = 0.0f;
+        if (i < N) {
+            cok[q] = order_coords(f, dir[0][i], dir[1][i], dir[2][i], cu[q], cv[q]);
+            order_grow_box(cok[q], cu[q], cv[q], umin, vmin, umax, vmax);
+        }
     }
     umin = -umin, vmin = -vmin;  // one max-reduction for all four
     block_reduce4max(umin, vmin, umax, vmax, red);
-    umin = -umin, vmin = -vmin;
-    const float su = umax > umin ? 63.999f / (umax - umin) : 0.0f;
-    const float sv = vmax > vmin ? 63.999f / (vmax - vmin) : 0.0f;
+    const OrderBox box = order_box(-umin, -vmin, umax, vmax);
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const int i = tid + q * 1024;
         if (i >= N) break;
-        int c = ACN_ORDER_BINS - 1;
-        if (cok[q]) {
-            const uint32_t qu = (uint32_t)fminf(fmaxf((cu[q] - umin) * su, 0.0f), 63.0f);
-            const uint32_t qv = (uint32_t)fminf(fmaxf((cv[q] - vmin) * sv, 0.0f), 63.0f);
-            c = (int)(spread6(qu) | (spread6(qv) << 1));
-        }
-        cell_of[i] = (uint16_t)c;
+        cell_of[i] = (uint16_t)order_cell(cok[q], cu[q], cv[q], box);
     }
     __syncthreads();  // dir[] is free from here on
     // Counting sort by cell, made stable per cell afterwards: histogram (LDS atomics), scan, an unordered
@@ -2473,6 +2412,48 @@ extern "C" int acn_ray_order(const float* rays, int64_t N, int32_t* order, void*
     return acn_check_launch("acn_ray_order");
 }
 
+// render_ws_kernel's selection prologue alone, on the render's grid: every workgroup writes the rays of its
+// windows, position -> ray index (acn_debug_ws_order; EXACT as ws_select_*)
+template <bool EXACT>
+__global__ void __launch_bounds__(1024) ws_order_debug_kernel(const float* __restrict__ rays, int N,
+                                                              int32_t* __restrict__ order) {
+    __shared__ __attribute__((aligned(16))) SelLds sel;
+    __shared__ uint16_t tab[kSelRounds * 16];
+    int64_t base, hi, stride;
+    xcd_band(N, 16, base, hi, stride);
+    SelRays sr;
+    ws_select_begin<EXACT>(rays, N, sr, sel);
+    __syncthreads();
+    ws_select_finish<EXACT>(sr, N, (int)base, (int)hi, (int)stride, sel, tab);
+    for (int k = 0; base < hi; base += stride, ++k) {
+        const int nr = (int)min((int64_t)16, hi - base);
+        if ((int)threadIdx.x < nr) order[base + threadIdx.x] = tab[k * 16 + threadIdx.x];
+    }
+}
+
+namespace {
+dim3 render_grid(int64_t N);
+bool ws_select_fits(int64_t N, unsigned grid);
+template <bool EXACT>
+int debug_ws_order(const float* rays, int64_t N, int32_t* order_out, void* stream) {
+    ACN_REQUIRE(N >= 1 && N <= ACN_ORDER_MAX, "acn_debug_ws_order: N must be in [1, %d], got %lld", ACN_ORDER_MAX,
+                (long long)N);
+    ACN_REQUIRE(rays && order_out, "acn_debug_ws_order: NULL pointer");
+    const dim3 grid = render_grid(N);
+    ACN_REQUIRE(ws_select_fits(N, grid.x), "acn_debug_ws_order: %lld rays on %u workgroups need more than %d rounds",
+                (long long)N, grid.x, kSelRounds);
+    hipLaunchKernelGGL(ws_order_debug_kernel<EXACT>, grid, dim3(1024), 0, (hipStream_t)stream, rays, (int)N, order_out);
+    return acn_check_launch("acn_debug_ws_order");
+}
+}  // namespace
+
+extern "C" int acn_debug_ws_order(const float* rays, int64_t N, int32_t* order_out, void* stream) {
+    return debug_ws_order<kWsExactFrame>(rays, N, order_out, stream);
+}
+extern "C" int acn_debug_ws_order_exact(const float* rays, int64_t N, int32_t* order_out, void* stream) {
+    return debug_ws_order<true>(rays, N, order_out, stream);
+}
+
 extern "C" int acn_pack_experts(const acn_expert* experts, const acn_routing* routing, int active_module,
                                 void* workspace, size_t workspace_bytes, void* stream) {
     FieldCfg cfg{};
@@ -2503,6 +2484,17 @@ extern "C" int acn_field_fwd(const float* x, int64_t M, int64_t ld, const acn_ex
 }
 
 namespace {
+// The stratified render's grid: a workgroup per 16 rays up to one per CU, in whole XCD bands (xcd_band)
+dim3 render_grid(int64_t N) {
+    int64_t wgs = (N + 15) / 16;
+    if ((num_cus() & 7) == 0) wgs = (wgs + 7) & ~(int64_t)7;
+    return dim3((unsigned)(wgs < num_cus() ? wgs : num_cus()));
+}
+// render_ws_kernel's slot table holds kSelRounds rounds of a workgroup: xcd_band's walk of N positions, 16 a round
+bool ws_select_fits(int64_t N, unsigned grid) {
+    const int64_t n = (grid & 7) == 0 ? (N + 7) >> 3 : N, stride = (int64_t)((grid & 7) == 0 ? grid >> 3 : grid) * 16;
+    return N <= ACN_ORDER_MAX && (n + stride - 1) / stride <= kSelRounds;
+}
 // The stratified render's kernel for one (interpolation, LDS-resident experts, routing) case.  Without early
 // termination (tau <= 0) and with S inside their LDS sample buffers, the depth-tiled kernels take the launch:
 // render_ws_kernel for one expert, render_wss_kernel for K > 2 (KL == 0; 16-ray rounds while S fits them).
@@ -2553,13 +2545,17 @@ extern "C" int acn_render_stratified_fwd_ordered(const float* rays, int64_t N, i
     if (st) return st;
     BgArgs b{bg->mode, bg->hidden, {bg->color[0], bg->color[1], bg->color[2]}, bg->w1, bg->b1, bg->w2, bg->b2};
     RenderParams p{rays, N, S, jitter, (const float*)workspace, sigma_scale, tau, rgb, depth, weights, acc, nullptr};
-    int64_t wgs = (N + 15) / 16;
-    if ((num_cus() & 7) == 0) wgs = (wgs + 7) & ~(int64_t)7;  // whole XCD bands (render_kernel)
-    const dim3 grid((unsigned)(wgs < num_cus() ? wgs : num_cus()));
+    const dim3 grid = render_grid(N);
     const bool slots = cfg.routing != 0 && K != 2;  // render_slots_kernel keeps its own order
     if (order_scratch && !slots && N <= ACN_ORDER_MAX && order_bytes >= (size_t)N * sizeof(int32_t)) {
-        hipLaunchKernelGGL(ray_order_kernel, dim3(1), dim3(1024), 0, s, rays, (int)N, (int32_t*)order_scratch);
-        p.order = (const int32_t*)order_scratch;
+        // render_ws_kernel (launch_render's condition) derives its windows of the order itself: no second kernel
+        const bool ws = cfg.routing == 0 && !(tau > 0.0f) && S <= kWsMaxS;
+        if (ws && ws_select_fits(N, grid.x)) {
+            p.ws_select = 1;
+        } else {
+            hipLaunchKernelGGL(ray_order_kernel, dim3(1), dim3(1024), 0, s, rays, (int)N, (int32_t*)order_scratch);
+            p.order = (const int32_t*)order_scratch;
+        }
     }
 #define ACN_RENDER_LAUNCH(I, KL, R) launch_render<I, KL, R>(grid, s, cfg, b, p)
     ACN_DISPATCH(ACN_RENDER_LAUNCH);

@@ -181,6 +181,15 @@ size_t acn_render_order_bytes(int64_t N);
  * and the order is the same on every call.  Exposed for tests and tools.                         */
 int acn_ray_order(const float* rays, int64_t N, int32_t* order, void* stream);
 
+/* The visiting order of the single-expert render without early termination (one expert, S <= 256, tau <= 0): its
+ * kernel derives the order itself, every workgroup the rays of its own 16-ray windows.  acn_debug_ws_order runs
+ * that step alone on the render's grid, as the render is built, and writes position -> ray index, a permutation
+ * of 0..N-1 (1 <= N <= 8192) sorted by (cell, ray index).  The step has two builds: the batch frame from
+ * acn_ray_order's reductions over all rays (the default; the cells and the order are then acn_ray_order's) or
+ * from 256 sampled rays.  acn_debug_ws_order_exact always runs the first.  For tests and tools.            */
+int acn_debug_ws_order(const float* rays, int64_t N, int32_t* order_out, void* stream);
+int acn_debug_ws_order_exact(const float* rays, int64_t N, int32_t* order_out, void* stream);
+
 /* acn_render_stratified_fwd with a caller-owned scratch of acn_render_order_bytes(N) bytes (NULL /
  * too small = no re-ordering).  Small batches are first sorted by ray direction (Z-order) so that
  * each XCD renders one compact image region and its L2 serves that region's hash cells; every ray
