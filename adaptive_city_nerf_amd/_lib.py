@@ -21,6 +21,7 @@ ACN_MAX_LEVELS = 32
 ACN_MAX_EXPERTS = 16
 ACN_BG_NONE, ACN_BG_CONST, ACN_BG_MLP = 0, 1, 2
 INTERP = {"Nearest": 0, "Linear": 1, "Smoothstep": 2}
+ACN_TABLE_F32, ACN_TABLE_F16 = 0, 1
 
 
 class AcnError(RuntimeError):
@@ -40,6 +41,7 @@ class acn_expert(C.Structure):
         ("col_w0", C.c_void_p), ("col_b0", C.c_void_p),
         ("col_w1", C.c_void_p), ("col_b1", C.c_void_p),
         ("col_w2", C.c_void_p), ("col_b2", C.c_void_p),
+        ("table_fmt", C.c_int32),
     ]
 
 
@@ -84,6 +86,8 @@ SIGNATURES = {
     "acn_sh_fwd": ([vp, i64, i32, vp, vp], C.c_int),
     "acn_hashgrid_bwd_input": ([vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp], C.c_int),
     "acn_sh_bwd": ([vp, i64, i32, vp, vp, vp], C.c_int),
+    "acn_expert_table_bytes": ([vp], sz),
+    "acn_table_to_f16": ([vp, i64, vp, vp], C.c_int),
     "acn_workspace_bytes": ([i32], sz),
     "acn_pack_experts": ([vp, vp, i32, vp, sz, vp], C.c_int),
     "acn_field_fwd": ([vp, i64, i64, vp, vp, i32, vp, sz, vp, vp], C.c_int),

@@ -347,6 +347,83 @@ __device__ __forceinline__ void hash_finish_x(const HashPendingX& p, float& o0, 
     hash_finish<INTERP>(h, o0, o1);
 }
 
+// The INTERP template value of the fused field also carries the table's storage format: 0 nearest, 1 linear,
+// 2 smoothstep on the fp32 table; 3 linear, 4 smoothstep on an fp16 copy of it (acn_expert.table_fmt; there is no
+// fp16 nearest).  The format is a compile-time property: one gather body per instantiation.
+constexpr int kInterpLinearF16 = 3, kInterpSmoothstepF16 = 4;
+constexpr bool interp_smooth(int interp) { return interp == 2 || interp == kInterpSmoothstepF16; }
+constexpr bool interp_f16(int interp) { return interp >= kInterpLinearF16; }
+
+// fp16 form of hash_issue_x / hash_finish_x: a row is two halves (4 bytes), so the x-paired block of rows
+// {i0 & ~1, i0 | 1} is ONE 8-byte gather and the second row of the odd-x0 lanes ONE 4-byte gather (out-of-range offset
+// for the others, as above).  Half the bytes in flight per level (12 dwords against 24), twice the rows per 128-B line.
+// The landed halves are widened with v_cvt_f32_f16, which is exact (fp16 subnormals included), and go through
+// hash_finish unchanged: the result equals, bit for bit, the fp32 gather of table.half().float().
+struct HashPendingH {
+    u32x2_t q[4];
+    uint32_t r[4];
+    float wx, wy, wz;
+    uint32_t sel;  // as HashPendingX
+};
+
+template <int INTERP>
+__device__ __forceinline__ void hash_issue_h(__amdgpu_buffer_rsrc_t rs, uint32_t lvbase, float sx, float sy, float sz,
+                                             uint32_t mask, HashPendingH& p) {
+    const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
+    float wx = sx - fx, wy = sy - fy, wz = sz - fz;
+    const uint32_t x0 = (uint32_t)(int)fx;
+    const uint32_t y0 = (uint32_t)(int)fy * kP1, y1 = y0 + kP1;
+    const uint32_t z0 = (uint32_t)(int)fz * kP2, z1 = z0 + kP2;
+    const uint32_t x1 = x0 + 1u;
+    if (interp_smooth(INTERP)) {
+        wx = (wx * wx) * (3.0f - 2.0f * wx);
+        wy = (wy * wy) * (3.0f - 2.0f * wy);
+        wz = (wz * wz) * (3.0f - 2.0f * wz);
+    }
+    const uint32_t aa[4] = {y0 ^ z0, y0 ^ z1, y1 ^ z0, y1 ^ z1};
+    const bool xodd = (x0 & 1u) != 0u;
+    uint32_t sel = xodd ? 16u : 0u;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t i0 = (x0 ^ aa[c]) & mask;
+        sel |= (i0 & 1u) << c;
+        p.q[c] = __builtin_amdgcn_raw_buffer_load_b64(rs, lvbase + ((i0 & ~1u) << 2), 0, 0);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t i1 = (x1 ^ aa[c]) & mask;
+        p.r[c] = __builtin_amdgcn_raw_buffer_load_b32(rs, xodd ? lvbase + (i1 << 2) : 0xFFFFFFF0u, 0, 0);
+    }
+    p.wx = wx;
+    p.wy = wy;
+    p.wz = wz;
+    p.sel = sel;
+}
+
+// one fp16 table row (low half = feature 0, high half = feature 1) widened to fp32
+__device__ __forceinline__ float2 row_f16(uint32_t v) {
+    return make_float2((float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xFFFFu)),
+                       (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16)));
+}
+
+template <int INTERP>
+__device__ __forceinline__ void hash_finish_h(const HashPendingH& p, float& o0, float& o1) {
+    HashPending h;
+    const bool xodd = (p.sel & 16u) != 0u;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const bool hi = ((p.sel >> c) & 1u) != 0u;
+        const u32x2_t q = p.q[c];
+        const uint32_t l = hi ? q[1] : q[0], e = hi ? q[0] : q[1];
+        h.f[2 * c] = row_f16(l);
+        h.f[2 * c + 1] = row_f16(xodd ? p.r[c] : e);
+    }
+    h.wx = p.wx;
+    h.wy = p.wy;
+    h.wz = p.wz;
+    hash_finish<INTERP>(h, o0, o1);
+}
+
 // One level of HashGridEncoder._torch_forward (encodings.py:331-381) for one point.
 // tl: this level's table base (row = F floats).  INTERP: 0 nearest, 1 linear, 2 smoothstep.
 // Linear/Smoothstep lerp order x -> y -> z exactly as encodings.py:373-379.

@@ -383,8 +383,29 @@ __device__ __forceinline__ int level_of(int i, int h) { return i + 8 * h; }
 template <int INTERP>
 __device__ __forceinline__ void hash_levels8(const ExpertMeta& em, int log2T, int h, float x0, float x1, float x2,
                                              float (&feat)[16]) {
-    constexpr int D = INTERP == 2 ? 1 : ACN_HASH_DEPTH;   // Smoothstep: one level in flight (its spill-free depth)
+    constexpr int D = interp_smooth(INTERP) ? 1 : ACN_HASH_DEPTH;   // Smoothstep: one level in flight (its spill-free depth)
     const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
+    if constexpr (interp_f16(INTERP)) {
+        // fp16 table: 4-byte rows, buffer form only (log2T <= 25 keeps the range in 32 bits)
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)em.table, (short)0, (int)(uint32_t)((16ull << log2T) * 4ull), 0x00020000);
+        HashPendingH ph[D];   // D as the fp32 form: 4 levels in flight measured no faster
+        auto issue_h = [&](int i, HashPendingH& pp) {
+            const int lv = level_of(i, h);
+            const float res = (float)(h ? em.res[8 + i] : em.res[i]);
+            hash_issue_h<INTERP>(rs, (uint32_t)lv << (log2T + 2), x0 * res, x1 * res, x2 * res, mask, pp);
+        };
+#pragma unroll
+        for (int l = 0; l < D - 1; ++l) issue_h(l, ph[l]);
+#pragma unroll
+        for (int l = 0; l < 8; ++l) {
+            if (l + D - 1 < 8) issue_h(l + D - 1, ph[(l + D - 1) % D]);
+            __builtin_amdgcn_sched_barrier(0);
+            hash_finish_h<INTERP>(ph[l % D], feat[2 * l], feat[2 * l + 1]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        return;
+    }
 #if ACN_XPAIR == 2
     if (INTERP != 0) {
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -2134,21 +2155,51 @@ int num_cus() {
     return g_num_cus;
 }
 
+// The table bytes the fused kernels address for this expert, or 0 with the status in *st: the one predicate of
+// acn_expert_table_bytes and check_expert, so an unsupported format is refused before any launch.  Host only.
+size_t expert_table_bytes(const acn_expert& e, int k, int* st) {
+    auto fail = [&](int code) { *st = code; return (size_t)0; };
+    *st = ACN_OK;
+    if (e.table_fmt != ACN_TABLE_F32 && e.table_fmt != ACN_TABLE_F16)
+        return fail(acn_set_error(ACN_ERR_UNSUPPORTED, "expert %d: unknown table_fmt %d", k, e.table_fmt));
+    if (e.L < 1 || e.L > ACN_MAX_LEVELS || e.F < 1 || e.log2T < 1 || e.log2T > 30)
+        return fail(acn_set_error(ACN_ERR_ARG, "expert %d: bad table shape (L=%d, F=%d, log2_hashmap_size=%d)", k, e.L,
+                                  e.F, e.log2T));
+    if (e.table_fmt == ACN_TABLE_F16) {
+        if (e.interp == ACN_INTERP_NEAREST)   // its gathers are the 64-bit-address ones
+            return fail(acn_set_error(ACN_ERR_UNSUPPORTED, "expert %d: fp16 tables are not rendered with Nearest", k));
+        if (e.L != 16 || e.F != 2)
+            return fail(acn_set_error(ACN_ERR_UNSUPPORTED, "expert %d: fp16 tables need levels*features = 16*2 (got %d*%d)",
+                                      k, e.L, e.F));
+        if (e.log2T > 25)   // 16 * 2^log2T rows of 4 bytes must stay inside the buffer resource's 32-bit range
+            return fail(acn_set_error(ACN_ERR_UNSUPPORTED, "expert %d: an fp16 table of log2_hashmap_size %d exceeds 2 GiB",
+                                      k, e.log2T));
+        return ((size_t)e.L << e.log2T) * (size_t)e.F * 2u;
+    }
+    return ((size_t)e.L << e.log2T) * (size_t)e.F * sizeof(float);
+}
+
 int check_expert(const acn_expert& e, int k) {
     ACN_REQUIRE(e.table, "expert %d: hash table is NULL", k);
     if (e.L != 16 || e.F != 2)
         return acn_set_error(ACN_ERR_UNSUPPORTED, "expert %d: fused path needs levels*features = 16*2 (got %d*%d)", k, e.L, e.F);
     ACN_REQUIRE(e.log2T >= 1 && e.log2T <= 30, "expert %d: log2_hashmap_size must be in [1, 30]", k);
     ACN_REQUIRE(e.interp >= 0 && e.interp <= 2, "expert %d: bad interpolation", k);
+    int st = ACN_OK;
+    if (expert_table_bytes(e, k, &st) == 0) return st;
     const float* ptrs[] = {e.sig_w0, e.sig_b0, e.sig_w1, e.sig_b1, e.sigh_w, e.sigh_b, e.geo_w,
                            e.geo_b, e.col_w0, e.col_b0, e.col_w1, e.col_b1, e.col_w2, e.col_b2};
     for (const float* q : ptrs) ACN_REQUIRE(q, "expert %d: NULL MLP weight/bias pointer", k);
     return ACN_OK;
 }
 
-// Builds FieldCfg + packs weights into the workspace.  Returns status; sets *interp.
+// Builds FieldCfg + packs weights into the workspace.  Returns status; sets *interp: the experts' interpolation, or
+// with fp16 tables the kernels' combined code (kInterpLinearF16 / kInterpSmoothstepF16).  f16_ok: the caller has the
+// fp16 instantiations (field forward, stratified renders); every other entry point refuses an fp16 expert here, so no
+// kernel ever reads an fp16 table as fp32.
 int prepare(const acn_expert* experts, const acn_routing* routing, int active_module, void* workspace,
-            size_t workspace_bytes, hipStream_t s, FieldCfg& cfg, int& interp, int& Keval, bool do_pack) {
+            size_t workspace_bytes, hipStream_t s, FieldCfg& cfg, int& interp, int& Keval, bool do_pack,
+            bool f16_ok = false) {
     ACN_REQUIRE(experts && routing, "NULL experts/routing");
     const int K = routing->K;
     ACN_REQUIRE(K >= 1 && K <= ACN_MAX_EXPERTS, "routing.K must be in [1, %d], got %d", ACN_MAX_EXPERTS, K);
@@ -2159,7 +2210,7 @@ int prepare(const acn_expert* experts, const acn_routing* routing, int active_mo
                 (size_t)Keval * PK_BYTES);
     ACN_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
     interp = experts[k0].interp;
-    const int log2T = experts[k0].log2T;
+    const int log2T = experts[k0].log2T, fmt = experts[k0].table_fmt;
     PackArgs pa{};
     for (int i = 0; i < Keval; ++i) {
         const acn_expert& e = experts[k0 + i];
@@ -2167,8 +2218,12 @@ int prepare(const acn_expert* experts, const acn_routing* routing, int active_mo
         if (st) return st;
         if (e.interp != interp || e.log2T != log2T)
             return acn_set_error(ACN_ERR_UNSUPPORTED, "experts must share interpolation and log2_hashmap_size");
+        if (e.table_fmt != fmt) return acn_set_error(ACN_ERR_UNSUPPORTED, "experts must share table_fmt");
+        if (fmt == ACN_TABLE_F16 && !f16_ok)
+            return acn_set_error(ACN_ERR_UNSUPPORTED, "expert %d: this entry point reads fp32 tables only (table_fmt = "
+                                 "ACN_TABLE_F16 is served by acn_field_fwd and acn_render_stratified_fwd[_ordered])", k0 + i);
         ExpertMeta& m = cfg.ex[i];
-        m.table = e.table;
+        m.table = (const float*)e.table;   // fp16 rows when fmt == ACN_TABLE_F16: only the *F16 instantiations read it
         for (int a = 0; a < 3; ++a) {
             m.amin[a] = e.aabb_min[a];
             m.ext[a] = e.aabb_extent[a];
@@ -2178,6 +2233,7 @@ int prepare(const acn_expert* experts, const acn_routing* routing, int active_mo
         pa.e[i] = PackSrc{e.sig_w0, e.sig_b0, e.sig_w1, e.sig_b1, e.sigh_w, e.sigh_b, e.geo_w, e.geo_b,
                           e.col_w0, e.col_b0, e.col_w1, e.col_b1, e.col_w2, e.col_b2};
     }
+    if (fmt == ACN_TABLE_F16) interp = interp == ACN_INTERP_SMOOTHSTEP ? kInterpSmoothstepF16 : kInterpLinearF16;
     cfg.K = Keval;
     cfg.log2T = log2T;
     cfg.cluster_2d = routing->cluster_2d;
@@ -2210,6 +2266,13 @@ int prepare(const acn_expert* experts, const acn_routing* routing, int active_mo
         if (interp == 1) ACN_DISPATCH_I(L, 1);                         \
         else if (interp == 0) ACN_DISPATCH_I(L, 0);                    \
         else ACN_DISPATCH_I(L, 2);                                     \
+    } while (0)
+// the entry points that also serve fp16 tables (prepare with f16_ok): two more instantiation families
+#define ACN_DISPATCH_FMT(L)                                            \
+    do {                                                               \
+        if (interp == kInterpLinearF16) ACN_DISPATCH_I(L, kInterpLinearF16);              \
+        else if (interp == kInterpSmoothstepF16) ACN_DISPATCH_I(L, kInterpSmoothstepF16); \
+        else ACN_DISPATCH(L);                                          \
     } while (0)
 
 // Training-path sampler: stratified_t_vals (ray_rendering.py:262-287, jitter from caller uniforms), the
@@ -2459,7 +2522,45 @@ extern "C" int acn_pack_experts(const acn_expert* experts, const acn_routing* ro
     FieldCfg cfg{};
     int interp, K;
     return prepare(experts, routing, active_module, workspace, workspace_bytes, (hipStream_t)stream, cfg, interp, K,
-                   true);
+                   true, true);   // packs the MLP weights only: either table format
+}
+
+namespace {
+// fp32 -> fp16 copy of a hash table, round to nearest even (v_cvt_f16_f32 under the default rounding and denormal
+// modes: subnormal results kept, overflow to inf, NaN stays NaN).  Four values per lane and step: one 16-byte load,
+// one 8-byte store; the n & 3 values of the tail go one per lane.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+__global__ void __launch_bounds__(256) table_to_f16_kernel(const float* __restrict__ src, int64_t n,
+                                                           _Float16* __restrict__ dst) {
+    const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const f32x4 v = ld4(src + 4 * i);
+        *reinterpret_cast<f16x4*>(dst + 4 * i) = f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+    }
+    const int64_t t = 4 * n4 + threadIdx.x;
+    if (blockIdx.x == 0 && t < n) dst[t] = (_Float16)src[t];
+}
+}  // namespace
+
+extern "C" int acn_table_to_f16(const float* src, int64_t n, void* dst, void* stream) {
+    ACN_REQUIRE(n >= 0, "acn_table_to_f16: n must be >= 0");
+    if (n == 0) return ACN_OK;
+    ACN_REQUIRE(src && dst, "acn_table_to_f16: NULL pointer");
+    ACN_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 7) == 0,
+                "acn_table_to_f16: src must be 16-byte and dst 8-byte aligned");
+    const int64_t wgs = ((n >> 2) + 255) / 256, cap = 8 * (int64_t)num_cus();
+    const dim3 grid((unsigned)(wgs < 1 ? 1 : (wgs < cap ? wgs : cap)));
+    hipLaunchKernelGGL(table_to_f16_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, n, (_Float16*)dst);
+    return acn_check_launch("acn_table_to_f16");
+}
+
+extern "C" size_t acn_expert_table_bytes(const acn_expert* e) {
+    if (!e) {
+        acn_set_error(ACN_ERR_ARG, "acn_expert_table_bytes: NULL expert");
+        return 0;
+    }
+    int st = ACN_OK;
+    return expert_table_bytes(*e, 0, &st);
 }
 
 extern "C" int acn_field_fwd(const float* x, int64_t M, int64_t ld, const acn_expert* experts,
@@ -2471,14 +2572,14 @@ extern "C" int acn_field_fwd(const float* x, int64_t M, int64_t ld, const acn_ex
     hipStream_t s = (hipStream_t)stream;
     FieldCfg cfg{};
     int interp, K;
-    int st = prepare(experts, routing, active_module, workspace, workspace_bytes, s, cfg, interp, K, false);
+    int st = prepare(experts, routing, active_module, workspace, workspace_bytes, s, cfg, interp, K, false, true);
     if (st) return st;
     FieldParams p{x, M, ld, (const float*)workspace, out};
     const int64_t ntiles = (M + 31) / 32;
     const int64_t wgs = (ntiles + 15) / 16;
     const dim3 grid((unsigned)(wgs < num_cus() ? wgs : num_cus())), block(1024);
 #define ACN_FIELD_LAUNCH(I, KL, R) hipLaunchKernelGGL((field_kernel<I, KL, R>), grid, block, 0, s, cfg, p)
-    ACN_DISPATCH(ACN_FIELD_LAUNCH);
+    ACN_DISPATCH_FMT(ACN_FIELD_LAUNCH);
 #undef ACN_FIELD_LAUNCH
     return acn_check_launch("acn_field_fwd");
 }
@@ -2541,7 +2642,7 @@ extern "C" int acn_render_stratified_fwd_ordered(const float* rays, int64_t N, i
     hipStream_t s = (hipStream_t)stream;
     FieldCfg cfg{};
     int interp, K;
-    int st = prepare(experts, routing, active_module, workspace, workspace_bytes, s, cfg, interp, K, false);
+    int st = prepare(experts, routing, active_module, workspace, workspace_bytes, s, cfg, interp, K, false, true);
     if (st) return st;
     BgArgs b{bg->mode, bg->hidden, {bg->color[0], bg->color[1], bg->color[2]}, bg->w1, bg->b1, bg->w2, bg->b2};
     RenderParams p{rays, N, S, jitter, (const float*)workspace, sigma_scale, tau, rgb, depth, weights, acc, nullptr};
@@ -2558,7 +2659,7 @@ extern "C" int acn_render_stratified_fwd_ordered(const float* rays, int64_t N, i
         }
     }
 #define ACN_RENDER_LAUNCH(I, KL, R) launch_render<I, KL, R>(grid, s, cfg, b, p)
-    ACN_DISPATCH(ACN_RENDER_LAUNCH);
+    ACN_DISPATCH_FMT(ACN_RENDER_LAUNCH);
 #undef ACN_RENDER_LAUNCH
     return acn_check_launch("acn_render_stratified_fwd");
 }

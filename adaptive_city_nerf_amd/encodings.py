@@ -232,6 +232,7 @@ class HashGridEncoder(nn.Module):
         if self.interpolation is not None and self.interpolation not in INTERPOLATIONS:
             self.interpolation = "Linear"
         self._interp_code = INTERP[self.interpolation or "Linear"]
+        self._render_table_dtype = torch.float32
 
     @property
     def out_dim(self) -> int:
@@ -239,6 +240,41 @@ class HashGridEncoder(nn.Module):
 
     def get_out_dim(self) -> int:
         return self._out_dim
+
+    def set_render_table_dtype(self, dtype: torch.dtype) -> None:
+        """Storage the no-grad field forward and the stratified eval renders gather from: ``torch.float32`` (the
+        default: the parameter itself) or ``torch.float16`` (an fp16 copy of it, half the bytes per corner; the
+        interpolation and everything after it stay fp32, so the outputs are those of ``hash_table.half().float()``
+        bit for bit).  Training, input gradients, the occupancy renderer, the expert-parallel renderer and this
+        encoder's own forward keep reading the fp32 parameter, which stays what it is (state-dict key, dtype, shape).
+        """
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"render table dtype must be torch.float32 or torch.float16, got {dtype!r}")
+        self._render_table_dtype = dtype
+        if dtype == torch.float32:
+            self.__dict__.pop("_render_shadow", None)
+
+    @property
+    def render_table_dtype(self) -> torch.dtype:
+        return self.__dict__.get("_render_table_dtype", torch.float32)
+
+    def render_table(self) -> torch.Tensor:
+        """The tensor the fused render kernels gather from under set_render_table_dtype: ``hash_table`` itself, or
+        its fp16 shadow.  The shadow is a plain attribute (no parameter, no buffer, not in state_dict), converted on
+        the current stream by acn_table_to_f16 and refreshed when the parameter's storage or version counter moved
+        (optimizer steps, in-place edits and load_state_dict all bump the version) -- the pack cache's rule."""
+        tab = self.hash_table
+        if self.render_table_dtype == torch.float32:
+            return tab
+        key = (tab.data_ptr(), tab._version, tab.device)
+        shadow = self.__dict__.get("_render_shadow")
+        if shadow is None or shadow[0] != key:
+            old = shadow[1] if shadow is not None else None
+            if old is not None and (old.shape != tab.shape or old.device != tab.device):
+                old = None
+            shadow = (key, ops.table_to_f16(tab, out=old))
+            self.__dict__["_render_shadow"] = shadow
+        return shadow[1]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         assert x.shape[-1] == 3, f"Expected (...,3), got {tuple(x.shape)}"

@@ -97,10 +97,18 @@ class MetaContainer(MetaModule):
             self._routing_key = key
         return self._routing_cache
 
-    def expert_specs(self, params=None) -> List[ops.ExpertSpec]:
+    def set_render_table_dtype(self, dtype: torch.dtype) -> None:
+        """Every expert's MetaNGP.set_render_table_dtype: torch.float16 makes the no-grad ``forward`` and the
+        stratified eval renders gather from fp16 copies of the hash tables; torch.float32 is the default."""
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"render table dtype must be torch.float32 or torch.float16, got {dtype!r}")
+        for sub in self.submodules:
+            sub.set_render_table_dtype(dtype)
+
+    def expert_specs(self, params=None, render_table: bool = False) -> List[ops.ExpertSpec]:
         K = len(self.submodules)
         sub = [self.get_subdict(params, f"submodules.{k}") for k in range(K)] if params is not None else [None] * K
-        return [self.submodules[k].expert_spec(sub[k]) for k in range(K)]
+        return [self.submodules[k].expert_spec(sub[k], render_table=render_table) for k in range(K)]
 
     def packed_weights(self, specs, routing, active_module=None, params=None):
         """Packed MFMA weight image for the fused kernels, cached while no owned weight changed."""
@@ -206,7 +214,7 @@ class MetaContainer(MetaModule):
         if active_module is not None:
             return self.submodules[active_module](x, params=sub_params[active_module])
         if not self.uses_grad(params) and not wants_grad(x) and all(s._fusable for s in self.submodules):
-            specs, routing = self.expert_specs(params), self.routing_spec()
+            specs, routing = self.expert_specs(params, render_table=True), self.routing_spec()
             return ops.field_fwd(x, specs, routing, packed=self.packed_weights(specs, routing, None, params))
         weights, hard = self._routing(x[:, :3])
         results = x.new_zeros(x.shape[0], self.dim_out)

@@ -170,25 +170,41 @@ class MetaNGP(MetaModule):
             self._box_key = key
         return self._box_cache
 
-    def expert_spec(self, params: Optional[Dict[str, Tensor]] = None) -> ops.ExpertSpec:
-        """Device description of this expert for the fused kernels (fast weights from params)."""
+    def set_render_table_dtype(self, dtype: torch.dtype) -> None:
+        """torch.float16: the no-grad ``forward`` and the stratified eval renders gather from an fp16 copy of the
+        hash table (HashGridEncoder.set_render_table_dtype); torch.float32 (default) restores the parameter."""
+        self.xyz_encoder.set_render_table_dtype(dtype)
+
+    def expert_spec(self, params: Optional[Dict[str, Tensor]] = None, render_table: bool = False) -> ops.ExpertSpec:
+        """Device description of this expert for the fused kernels (fast weights from params).  ``render_table``:
+        the caller is the field forward or a stratified render, whose kernels also serve the encoder's fp16 render
+        table; every other caller (occupancy renderer, expert-parallel renderer, ``density``) gets the fp32 table
+        whatever set_render_table_dtype selected."""
         if not self._fusable:
             raise ops.AcnError("the fused HIP field implements the reference configuration (L=16, F=2, sigma 2x64, "
                                "geo 15, SH-4, colour 2x64, sigmoid rgb; nerf_runner.py:102-121)")
         enc = self.xyz_encoder
         mn, ext = self._host_box()
         mlp = self._mlp_tensors(params)
+        f16 = render_table and enc.render_table_dtype == torch.float16
+        fmt = ops._lib.ACN_TABLE_F16 if f16 else ops._lib.ACN_TABLE_F32
+        if f16 and enc._interp_code == 0:   # before the shadow is built: acn_expert_table_bytes would refuse it too
+            raise ops.AcnError("fp16 render tables are not rendered with Nearest interpolation (its gathers are the "
+                               "64-bit-address form); set_render_table_dtype(torch.float32) for this encoder")
+        table = enc.render_table() if f16 else enc.hash_table
         if params is not None or not all(t.dtype == torch.float32 and t.is_contiguous()
                                          for t in [enc.hash_table, *mlp.values()]):   # copies: never cached
-            return ops.ExpertSpec(enc.hash_table, enc._res_host, enc.log2_hashmap_size, enc._interp_code, mn, ext, mlp)
+            return ops.ExpertSpec(table, enc._res_host, enc.log2_hashmap_size, enc._interp_code, mn, ext, mlp,
+                                  table_fmt=fmt)
         # module weights: the spec holds pointers only, so it is reused while every tensor keeps its storage
-        key = (self._box_key, enc.hash_table.data_ptr(), enc.log2_hashmap_size, enc._interp_code,
+        key = (self._box_key, table.data_ptr(), fmt, enc.log2_hashmap_size, enc._interp_code,
                tuple(enc._res_host)) + tuple((id(t), t.data_ptr()) for t in mlp.values())
-        cache = self.__dict__.get("_spec_cache")
+        name = "_spec_cache_f16" if f16 else "_spec_cache"
+        cache = self.__dict__.get(name)
         if cache is None or cache[0] != key:
-            cache = (key, ops.ExpertSpec(enc.hash_table, enc._res_host, enc.log2_hashmap_size, enc._interp_code, mn,
-                                         ext, mlp))
-            self.__dict__["_spec_cache"] = cache
+            cache = (key, ops.ExpertSpec(table, enc._res_host, enc.log2_hashmap_size, enc._interp_code, mn, ext, mlp,
+                                         table_fmt=fmt))
+            self.__dict__[name] = cache
         return cache[1]
 
     def packed_weights(self, spec, routing, params=None):
@@ -216,7 +232,7 @@ class MetaNGP(MetaModule):
             # no autograd (occupancy updates / marching visibility): the fused field kernel; the
             # direction input only feeds the colour branch, whose output is dropped
             flat = x.reshape(-1, 3)
-            sig = self.forward(torch.cat([flat, torch.zeros_like(flat)], dim=-1), params=params)[:, 3:4]
+            sig = self._fused_forward(torch.cat([flat, torch.zeros_like(flat)], dim=-1), params, False)[:, 3:4]
             return sig.reshape(*x.shape[:-1], 1)
         h = self._enc_xyz(x)
         h = self.sigma_trunk(h, params=self.get_subdict(params, "sigma_trunk"))
@@ -237,17 +253,22 @@ class MetaNGP(MetaModule):
         return (_FusedMLPFn.INPUT_GRAD_FUSED and ops.TRAIN_MLP_PRECISION != "amp"
                 and not wants_grad(*self._mlp_tensors(params).values()))
 
+    def _fused_forward(self, x_d: Tensor, params, render_table: bool) -> Tensor:
+        """The no-grad field on the fused kernel; render_table: gather from the encoder's render table (forward),
+        or from the fp32 parameter whatever the switch says (density: occupancy updates and marching)."""
+        from ._lib import acn_routing
+        r = acn_routing()
+        r.K, r.cluster_2d, r.boundary_margin = 1, 1, 1.0
+        flat = x_d.reshape(-1, 6)
+        spec = self.expert_spec(params, render_table=render_table)
+        return ops.field_fwd(flat, [spec], r, active_module=0,
+                             packed=self.packed_weights(spec, r, params)).view(*x_d.shape[:-1], 4)
+
     def forward(self, x_d: Tensor, params=None) -> Tensor:
         """[xyz(3), dir(3)] -> [rgb(3), sigma(1)] (meta_ngp.py:226-241)."""
         assert x_d.shape[-1] == 6, f"Expected (...,6) [xyz,dir], got {x_d.shape}"
         if self._fusable and not self.uses_grad(params) and not wants_grad(x_d):
-            from ._lib import acn_routing
-            r = acn_routing()
-            r.K, r.cluster_2d, r.boundary_margin = 1, 1, 1.0
-            flat = x_d.reshape(-1, 6)
-            spec = self.expert_spec(params)
-            return ops.field_fwd(flat, [spec], r, active_module=0,
-                                 packed=self.packed_weights(spec, r, params)).view(*x_d.shape[:-1], 4)
+            return self._fused_forward(x_d, params, True)
         x, d = x_d[..., :3], x_d[..., 3:6]
         if self._fused_train_ok(x_d, params):
             # training: hash grid (HIP, autograd to the table and the points) + the whole MLP fwd/bwd on MFMA

@@ -119,6 +119,20 @@ def hashgrid_bwd_input(x01: torch.Tensor, grad_out: torch.Tensor, table: torch.T
     return gx.view(*x01.shape[:-1], 3)
 
 
+def table_to_f16(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp16 copy of an fp32 tensor, round to nearest even (acn_table_to_f16), on the current stream; written into
+    ``out`` (a contiguous float16 tensor of the same shape and device) when given.  The render-table shadow of
+    HashGridEncoder.set_render_table_dtype."""
+    require_hip(src, "table_to_f16")
+    s = _f32(src)
+    if out is None:
+        out = torch.empty(s.shape, device=s.device, dtype=torch.float16)
+    elif out.dtype != torch.float16 or out.shape != s.shape or out.device != s.device or not out.is_contiguous():
+        raise ValueError("table_to_f16: out must be a contiguous float16 tensor of src's shape on src's device")
+    check(_lib.lib().acn_table_to_f16(ptr(s), s.numel(), ptr(out), stream_of(s)), "acn_table_to_f16")
+    return out
+
+
 def sh_bwd(d: torch.Tensor, g_out: torch.Tensor, levels: int) -> torch.Tensor:
     """Gradient of sh_fwd in the (unnormalised) directions, (..., 3) fp32 (acn_sh_bwd)."""
     require_hip(d, "SHEncoder")
@@ -144,20 +158,41 @@ def sh_fwd(d: torch.Tensor, levels: int) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------
 class ExpertSpec:
     """The device-side description of one MetaNGP expert: hash table + level resolutions + AABB +
-    the 14 MLP tensors (module parameters or fast weights from a `params` dict)."""
+    the 14 MLP tensors (module parameters or fast weights from a `params` dict).  ``table_fmt``
+    ACN_TABLE_F16: ``table`` is the fp16 copy of the hash table (table_to_f16), for the field forward and the
+    stratified renders only; a combination the kernels refuse (acn_expert_table_bytes) raises here, before any
+    launch, and so does a table tensor smaller than the kernels will address."""
 
     def __init__(self, table: torch.Tensor, resolutions: Sequence[int], log2T: int, interp: int,
                  aabb_min: Sequence[float], aabb_extent: Sequence[float], mlp: Dict[str, torch.Tensor],
-                 F: int = 2):
+                 F: int = 2, table_fmt: int = _lib.ACN_TABLE_F32):
         self.keep = []
         s = acn_expert()
-        tab = _f32(table)
+        if int(table_fmt) == _lib.ACN_TABLE_F16:
+            if table.dtype != torch.float16:
+                raise AcnError(f"table_fmt ACN_TABLE_F16 needs a float16 table, got {table.dtype}")
+            tab = table.detach().contiguous()
+        else:
+            tab = _f32(table)
         self.keep.append(tab)
         s.table = ptr(tab)
         s.L = len(resolutions)
         s.log2T = int(log2T)
         s.F = int(F)
         s.interp = int(interp)
+        s.table_fmt = int(table_fmt)
+        table_bytes = getattr(_lib.lib(), "acn_expert_table_bytes", None)
+        if table_bytes is None:   # a developer library (ACNERF_LIB) from before table_fmt: fp32 experts only
+            if s.table_fmt != _lib.ACN_TABLE_F32:
+                raise AcnError(f"{_lib.LIB_PATH} predates acn_expert.table_fmt: fp32 tables only")
+            need = 0
+        else:
+            need = int(table_bytes(C.byref(s)))
+            if need == 0:   # the refusal's message is in acn_last_error
+                check(-2, "acn_expert_table_bytes")
+        if tab.numel() * tab.element_size() < need:
+            raise AcnError(f"hash table holds {tab.numel() * tab.element_size()} bytes, the fused kernels address "
+                           f"{need} (L={s.L}, log2T={s.log2T}, F={s.F}, table_fmt={s.table_fmt})")
         for i, r in enumerate(resolutions):
             s.res[i] = int(r)
         s.aabb_min[:] = [float(v) for v in aabb_min]

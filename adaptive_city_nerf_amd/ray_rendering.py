@@ -317,8 +317,10 @@ def _render_routed(model, rays: Tensor, S: int, params, u: Optional[Tensor], bg_
     return volume_render(rgb_sigma, t_vals, bg_rgb=bg_rgb, raw_rgb=False, raw_sigma=False, sigma_scale=sigma_scale)
 
 
-def _fused_experts(model, params, active_module):
-    """(specs, routing) for the fused kernels, or None if the model/config is not fusable."""
+def _fused_experts(model, params, active_module, render_table: bool = False):
+    """(specs, routing, packed weights) for the fused kernels, or None if the model/config is not fusable.
+    render_table: the stratified render, which also serves the experts' fp16 render tables
+    (set_render_table_dtype); the occupancy renderers keep the fp32 tables."""
     if isinstance(model, MetaContainer):
         if not all(s._fusable for s in model.submodules):
             return None
@@ -328,18 +330,18 @@ def _fused_experts(model, params, active_module):
                 return None
             r = acn_routing()
             r.K, r.cluster_2d, r.boundary_margin = 1, 1, 1.0
-            spec = sub.expert_spec(params)
+            spec = sub.expert_spec(params, render_table=render_table)
             return [spec], r, sub.packed_weights(spec, r, params)
         if model.uses_grad(params):
             return None
-        specs, routing = model.expert_specs(params), model.routing_spec()
+        specs, routing = model.expert_specs(params, render_table=render_table), model.routing_spec()
         return specs, routing, model.packed_weights(specs, routing, None, params)
     if isinstance(model, MetaNGP):
         if not model._fusable or model.uses_grad(params):
             return None
         r = acn_routing()
         r.K, r.cluster_2d, r.boundary_margin = 1, 1, 1.0
-        spec = model.expert_spec(params)
+        spec = model.expert_spec(params, render_table=render_table)
         return [spec], r, model.packed_weights(spec, r, params)
     return None
 
@@ -372,7 +374,7 @@ def render_rays_stratified(model, rays: Tensor, ray_samples: int, params=None, a
     want_weights = bool(kwargs.get("_want_weights", True))  # render_image drops the (N,S) weights
     N = rays.shape[0]
     if rays.is_cuda and not diff_rays:
-        fe = _fused_experts(model, params, active_module)
+        fe = _fused_experts(model, params, active_module, render_table=True)
         fb = _fused_background(model, bg_color_default, N, rays.device) if fe is not None else None
         if fe is not None and fb is not None:
             specs, routing, packed = fe

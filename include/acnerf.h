@@ -38,6 +38,10 @@ extern "C" {
 #define ACN_INTERP_LINEAR 1
 #define ACN_INTERP_SMOOTHSTEP 2
 
+/* storage format of acn_expert.table */
+#define ACN_TABLE_F32 0            /* the reference's fp32 parameter (every entry point) */
+#define ACN_TABLE_F16 1            /* an fp16 copy of it (acn_table_to_f16): field forward and stratified renders */
+
 /* One Instant-NGP expert (MetaNGP, models/inr/meta_ngp.py:15-241).  Pointers are device memory
  * holding the reference's own tensors (state-dict layout, nn.Linear weights (out, in) row-major),
  * or the fast weights of a `params` dict (models/metamodule/metamodule.py:140-156).
@@ -45,7 +49,8 @@ extern "C" {
  * L*F = 32 hash features, sigma_trunk 2 x 64 (ReLU), sigma_head 64->1, geo_head 64->15,
  * SH levels 4 (16 comps), color_mlp 31->64->64 (ReLU) ->3, sigmoid rgb.                       */
 typedef struct acn_expert {
-    const float* table;            /* xyz_encoder.hash_table (L << log2T, F) */
+    const void* table;             /* xyz_encoder.hash_table (L << log2T, F): float rows, or with table_fmt ==
+                                      ACN_TABLE_F16 rows of F halves (acn_table_to_f16 of that tensor) */
     int32_t L, log2T, F, interp;
     int32_t res[ACN_MAX_LEVELS];   /* xyz_encoder.level_resolutions (host values) */
     float aabb_min[3];             /* scene_box.min               (meta_ngp.py:157) */
@@ -57,6 +62,14 @@ typedef struct acn_expert {
     const float *col_w0, *col_b0;  /* color_mlp.0.linear    (64, 31), (64,) */
     const float *col_w1, *col_b1;  /* color_mlp.1.linear    (64, 64), (64,) */
     const float *col_w2, *col_b2;  /* color_mlp.2           (3, 64),  (3,)  */
+    int32_t table_fmt;             /* ACN_TABLE_F32 (0: a zero-initialised struct is an fp32 expert) or ACN_TABLE_F16.
+                                      With ACN_TABLE_F16, acn_field_fwd and acn_render_stratified_fwd[_ordered] gather
+                                      4-byte rows and widen them to fp32 (exact), then interpolate in fp32 as always:
+                                      the outputs equal, bit for bit, those of the fp32 table holding the same rounded
+                                      values.  Needs Linear or Smoothstep, L = 16, F = 2, log2T <= 25, experts of one
+                                      call sharing the format.  Every other entry point taking acn_expert (packed
+                                      occupancy render, expert-parallel field) returns ACN_ERR_UNSUPPORTED for it;
+                                      acn_pack_experts reads no table and accepts both. */
 } acn_expert;
 
 /* MetaContainer routing (models/inr/meta_container.py:97-134): soft inverse-distance weights
@@ -116,6 +129,19 @@ int acn_hashgrid_bwd_input(const float* x01, int64_t M, const float* grad_out, c
  * norm and clamp_min: g_d = (g_n - n (n.g_n)) / |d| for |d| >= 1e-9, else g_n / 1e-9).
  * g_out (M, levels^2) -> g_d (M,3), overwritten; levels in [1, 5] (levels == 1 gives zeros).     */
 int acn_sh_bwd(const float* d, int64_t M, int levels, const float* g_out, float* g_d, void* stream);
+
+/* Host only (no HIP call): the number of bytes at e->table the fused kernels address for this expert --
+ * (L << log2T) * F * 4 for ACN_TABLE_F32, * 2 for ACN_TABLE_F16 -- so a caller can check its allocation before a
+ * launch.  Returns 0 and sets acn_last_error for a combination the kernels refuse: an unknown table_fmt, or
+ * ACN_TABLE_F16 with Nearest, with F != 2 or L != 16, or with log2T > 25 (more than 2 GiB: the fp16 gathers are
+ * buffer loads with 32-bit offsets).  The field / render entry points apply the same predicate before launching. */
+size_t acn_expert_table_bytes(const acn_expert* e);
+
+/* dst[i] = (fp16) src[i], i < n, round to nearest even (fp16 subnormals produced, overflow to inf, NaN stays NaN):
+ * the ACN_TABLE_F16 copy of a hash table, n = (L << log2T) * F.  Runs on `stream` like every other call, so a
+ * conversion queued after an optimizer step and before a render needs no host synchronisation.  Any n >= 0; src
+ * 16-byte aligned, dst 8-byte aligned (2 n bytes). */
+int acn_table_to_f16(const float* src, int64_t n, void* dst, void* stream);
 
 /* Bytes of device workspace the fused field / render entry points need for K experts. */
 size_t acn_workspace_bytes(int K);
