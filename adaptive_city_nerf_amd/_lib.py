@@ -85,6 +85,8 @@ SIGNATURES = {
     "acn_hashgrid_bwd": ([vp, i64, vp, vp, i32, i32, i32, i32, vp, vp], C.c_int),
     "acn_sh_fwd": ([vp, i64, i32, vp, vp], C.c_int),
     "acn_hashgrid_bwd_input": ([vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp], C.c_int),
+    "acn_hashgrid_bwd_input_bwd": ([vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp], C.c_int),
+    "acn_hashgrid_bwd_input_bwd_table": ([vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp], C.c_int),
     "acn_sh_bwd": ([vp, i64, i32, vp, vp, vp], C.c_int),
     "acn_expert_table_bytes": ([vp], sz),
     "acn_table_to_f16": ([vp, i64, vp, vp], C.c_int),

@@ -651,6 +651,284 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_input_gen(const float* __res
     gx[3 * m + 2] = a.z;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Double backward of the input gradient: with t = gg_x (M,3) the cotangent of grad_x, the
+// derivatives of sum_a t_a grad_x[a] in grad_out (gather), in the points (gather) and in the table (scatter).  Per
+// level, u the raw weights, w = S(u), X/Y/Z(b) the corner's weight per axis (w or 1 - w), sgn(b) = +-1:
+//   p_a     = (t_a * res) * S'(u_a)
+//   k_b     = p_x sgn_x Y Z + p_y X sgn_y Z + p_z X Y sgn_z                   (replaces the trilinear weight)
+//   gg[f]   = sum_b k_b row_b[f],      grad_table[row_b, f] += k_b * g[f]
+//   g_x[e]  = res^2 (S'(u_e) sum_{a != e} t_a S'(u_a) H_ae + t_e S''(u_e) G_e)
+// G_e the first and H_ae the mixed second differences of the folded corner values V_b = sum_f g[f] row_b[f] (the
+// trilinear form has no pure second derivative, so Linear keeps the H terms only).
+struct AxisW {
+    float w, a, d1, d2;   // S(u), 1 - S(u), S'(u), S''(u)
+};
+
+// Every member keeps its relative accuracy: 1 - u and 1 - 2u are exact where they cancel, and the complement of
+// the smoothed weight is S(1 - u), not 1 - S(u) (whose rounding is absolute: as the weight of a single corner in
+// the table scatter it would miss the per-row bound next to w = 1).
+template <int INTERP>
+__device__ __forceinline__ AxisW axis_w(float u) {
+    const float q = 1.0f - u;
+    if (INTERP == 2)
+        return AxisW{(u * u) * (3.0f - 2.0f * u), (q * q) * (3.0f - 2.0f * q), (6.0f * u) * q, 6.0f * (1.0f - 2.0f * u)};
+    return AxisW{u, q, 1.0f, 0.0f};
+}
+
+// k_b of one corner: X, Y, Z its weights per axis, bx / by / bz its bits
+__device__ __forceinline__ float corner_k(float px, float py, float pz, float X, float Y, float Z, bool bx, bool by,
+                                          bool bz) {
+    const float tx = px * (Y * Z), ty = py * (X * Z), tz = pz * (X * Y);
+    return ((bx ? tx : -tx) + (by ? ty : -ty)) + (bz ? tz : -tz);
+}
+
+// k[] in hash_issue's order (bit0 = x1, bit1 = z1, bit2 = y1)
+__device__ __forceinline__ void corner_ks(const AxisW& X, const AxisW& Y, const AxisW& Z, float r, float tx, float ty,
+                                          float tz, float (&k)[8]) {
+    const float px = (tx * r) * X.d1, py = (ty * r) * Y.d1, pz = (tz * r) * Z.d1;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const bool bx = (c & 1) != 0, bz = (c & 2) != 0, by = (c & 4) != 0;
+        k[c] = corner_k(px, py, pz, bx ? X.w : X.a, by ? Y.w : Y.a, bz ? Z.w : Z.a, bx, by, bz);
+    }
+}
+
+// v[]: the folded corner values in hash_issue's order
+template <int INTERP>
+__device__ __forceinline__ LevelGrad level_hess(const float (&v)[8], const AxisW& X, const AxisW& Y, const AxisW& Z,
+                                                float r, float tx, float ty, float tz) {
+    const float wx = X.w, wy = Y.w, wz = Z.w;
+    const float ax = X.a, ay = Y.a, az = Z.a;
+    const float c00 = v[0] * ax + v[1] * wx, c01 = v[2] * ax + v[3] * wx;   // c{y}{z}: the forward's x-lerps
+    const float c10 = v[4] * ax + v[5] * wx, c11 = v[6] * ax + v[7] * wx;
+    const float d00 = v[1] - v[0], d01 = v[3] - v[2], d10 = v[5] - v[4], d11 = v[7] - v[6];
+    const float hxy = (d10 - d00) * az + (d11 - d01) * wz;
+    const float hxz = (d01 - d00) * ay + (d11 - d10) * wy;
+    const float hyz = (c11 - c01) - (c10 - c00);
+    const float px = tx * X.d1, py = ty * Y.d1, pz = tz * Z.d1;
+    float ex = X.d1 * (py * hxy + pz * hxz);
+    float ey = Y.d1 * (px * hxy + pz * hyz);
+    float ez = Z.d1 * (px * hxz + py * hyz);
+    if (INTERP == 2) {
+        const float gx = (d00 * ay + d10 * wy) * az + (d01 * ay + d11 * wy) * wz;
+        const float gy = (c10 - c00) * az + (c11 - c01) * wz;
+        const float gz = (c01 * ay + c11 * wy) - (c00 * ay + c10 * wy);
+        ex += (tx * X.d2) * gx;
+        ey += (ty * Y.d2) * gy;
+        ez += (tz * Z.d2) * gz;
+    }
+    const float r2 = r * r;
+    return LevelGrad{r2 * ex, r2 * ey, r2 * ez};
+}
+
+// one level of the F == 2 buffer form: gg (when want_gg) and the level's g_x term (when want_gx, else zeros)
+template <int INTERP>
+__device__ __forceinline__ LevelGrad level_hess_f2(__amdgpu_buffer_rsrc_t rs, int l, int log2T, uint32_t mask,
+                                                   float r, float px, float py, float pz, float2 g, float tx,
+                                                   float ty, float tz, bool want_gg, bool want_gx, float2& gg) {
+    const float sx = px * r, sy = py * r, sz = pz * r;
+    acn::HashPendingX p;
+    acn::hash_issue_x<INTERP>(rs, (uint32_t)l << (log2T + 3), sx, sy, sz, mask, p);
+    float2 f[8];
+    acn::hash_rows_x(p, f);
+    const AxisW X = axis_w<INTERP>(sx - floorf(sx)), Y = axis_w<INTERP>(sy - floorf(sy)),
+                Z = axis_w<INTERP>(sz - floorf(sz));
+    if (want_gg) {
+        float k[8];
+        corner_ks(X, Y, Z, r, tx, ty, tz, k);
+        float s0 = k[0] * f[0].x, s1 = k[0] * f[0].y;
+#pragma unroll
+        for (int c = 1; c < 8; ++c) {
+            s0 += k[c] * f[c].x;
+            s1 += k[c] * f[c].y;
+        }
+        gg = make_float2(s0, s1);
+    }
+    if (!want_gx) return LevelGrad{0.0f, 0.0f, 0.0f};
+    float v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = g.x * f[c].x + g.y * f[c].y;
+    return level_hess<INTERP>(v, X, Y, Z, r, tx, ty, tz);
+}
+
+// ggout / gx2: either may be null (uniform)
+template <int INTERP, bool TREE>
+__global__ void __launch_bounds__(256) hashgrid_bwd_input_bwd_f2(const float* __restrict__ x01, int64_t M,
+                                                                 const float2* __restrict__ gout,
+                                                                 const float* __restrict__ ggx,
+                                                                 const float2* __restrict__ table, Res32 res, int L,
+                                                                 int log2T, float2* __restrict__ ggout,
+                                                                 float* __restrict__ gx2) {
+    const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)table, (short)0, (int)((uint32_t)L << (log2T + 3)), 0x00020000);
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool want_gg = ggout != nullptr, want_gx = gx2 != nullptr;
+    if (TREE) {
+        // one lane per (point, level), as hashgrid_bwd_input_f2: gg is the lane's own, the g_x terms take the tree
+        const int64_t m = gid / L;
+        const int l = (int)(gid - m * L);
+        LevelGrad a{0.0f, 0.0f, 0.0f};
+        if (m < M) {
+            float2 gg;
+            a = level_hess_f2<INTERP>(rs, l, log2T, mask, (float)res.v[l], x01[3 * m], x01[3 * m + 1], x01[3 * m + 2],
+                                      gout[m * L + l], ggx[3 * m], ggx[3 * m + 1], ggx[3 * m + 2], want_gg, want_gx, gg);
+            if (want_gg) ggout[m * L + l] = gg;
+        }
+        if (!want_gx) return;
+        for (int off = 1; off < L; off <<= 1) {
+            a.x += __shfl_xor(a.x, off);
+            a.y += __shfl_xor(a.y, off);
+            a.z += __shfl_xor(a.z, off);
+        }
+        if (m < M && l == 0) {
+            gx2[3 * m] = a.x;
+            gx2[3 * m + 1] = a.y;
+            gx2[3 * m + 2] = a.z;
+        }
+    } else {
+        const int64_t m = gid;
+        if (m >= M) return;
+        const float px = x01[3 * m], py = x01[3 * m + 1], pz = x01[3 * m + 2];
+        const float tx = ggx[3 * m], ty = ggx[3 * m + 1], tz = ggx[3 * m + 2];
+        LevelGrad a{0.0f, 0.0f, 0.0f};
+        for (int l = 0; l < L; ++l) {
+            float2 gg;
+            const LevelGrad t = level_hess_f2<INTERP>(rs, l, log2T, mask, (float)res.v[l], px, py, pz, gout[m * L + l],
+                                                      tx, ty, tz, want_gg, want_gx, gg);
+            if (want_gg) ggout[m * L + l] = gg;
+            a.x += t.x;
+            a.y += t.y;
+            a.z += t.z;
+        }
+        if (want_gx) {
+            gx2[3 * m] = a.x;
+            gx2[3 * m + 1] = a.y;
+            gx2[3 * m + 2] = a.z;
+        }
+    }
+}
+
+// any F, any table size: 64-bit row addresses, one lane per point
+template <int INTERP>
+__global__ void __launch_bounds__(256) hashgrid_bwd_input_bwd_gen(const float* __restrict__ x01, int64_t M,
+                                                                  const float* __restrict__ gout,
+                                                                  const float* __restrict__ ggx,
+                                                                  const float* __restrict__ table, Res32 res, int L,
+                                                                  int log2T, int F, float* __restrict__ ggout,
+                                                                  float* __restrict__ gx2) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
+    const float px = x01[3 * m], py = x01[3 * m + 1], pz = x01[3 * m + 2];
+    const float tx = ggx[3 * m], ty = ggx[3 * m + 1], tz = ggx[3 * m + 2];
+    LevelGrad a{0.0f, 0.0f, 0.0f};
+    for (int l = 0; l < L; ++l) {
+        const float r = (float)res.v[l];
+        const float sx = px * r, sy = py * r, sz = pz * r;
+        const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
+        const uint32_t x0 = (uint32_t)(int)fx, x1 = x0 + 1u;
+        const uint32_t y0 = (uint32_t)(int)fy * acn::kP1, y1 = y0 + acn::kP1;
+        const uint32_t z0 = (uint32_t)(int)fz * acn::kP2, z1 = z0 + acn::kP2;
+        const uint32_t rows[8] = {x0 ^ y0 ^ z0, x1 ^ y0 ^ z0, x0 ^ y0 ^ z1, x1 ^ y0 ^ z1,
+                                  x0 ^ y1 ^ z0, x1 ^ y1 ^ z0, x0 ^ y1 ^ z1, x1 ^ y1 ^ z1};
+        const float* tl = table + ((int64_t)l << log2T) * F;
+        const float* g = gout + (m * L + l) * F;
+        const AxisW X = axis_w<INTERP>(sx - fx), Y = axis_w<INTERP>(sy - fy), Z = axis_w<INTERP>(sz - fz);
+        if (ggout) {
+            float k[8];
+            corner_ks(X, Y, Z, r, tx, ty, tz, k);
+            float* o = ggout + (m * L + l) * F;
+            for (int f = 0; f < F; ++f) {
+                float s = 0.0f;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) s += k[c] * tl[(int64_t)(rows[c] & mask) * F + f];
+                o[f] = s;
+            }
+        }
+        if (gx2) {
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const float* e = tl + (int64_t)(rows[c] & mask) * F;
+                float s = 0.0f;
+                for (int f = 0; f < F; ++f) s += g[f] * e[f];
+                v[c] = s;
+            }
+            const LevelGrad t = level_hess<INTERP>(v, X, Y, Z, r, tx, ty, tz);
+            a.x += t.x;
+            a.y += t.y;
+            a.z += t.z;
+        }
+    }
+    if (gx2) {
+        gx2[3 * m] = a.x;
+        gx2[3 * m + 1] = a.y;
+        gx2[3 * m + 2] = a.z;
+    }
+}
+
+// The table side, F == 2: hashgrid_bwd_f2's lane mapping (4 points x 8 corners x 2 features per wave at one level),
+// k_b in place of the trilinear weight.
+template <int INTERP>
+__global__ void __launch_bounds__(256) hashgrid_bwd_input_bwd_table_f2(const float* __restrict__ x01, int64_t M,
+                                                                       const float* __restrict__ gout,
+                                                                       const float* __restrict__ ggx, Res32 res, int L,
+                                                                       int log2T, float* __restrict__ gtable) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t groups = (M + 3) >> 2;               // groups of 4 points
+    const int l = (int)(wave / groups);
+    const int64_t m = (wave - (int64_t)l * groups) * 4 + (lane >> 4);
+    if (l >= L || m >= M) return;
+    const int f = lane & 1;
+    const bool bx = ((lane >> 1) & 1) != 0, by = ((lane >> 3) & 1) != 0, bz = ((lane >> 2) & 1) != 0;
+    const float r = (float)res.v[l];
+    const float sx = x01[3 * m] * r, sy = x01[3 * m + 1] * r, sz = x01[3 * m + 2] * r;
+    const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
+    const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
+    const AxisW X = axis_w<INTERP>(sx - fx), Y = axis_w<INTERP>(sy - fy), Z = axis_w<INTERP>(sz - fz);
+    const uint32_t xi = (uint32_t)(int)fx + (bx ? 1u : 0u);
+    const uint32_t yi = (uint32_t)(int)fy * acn::kP1 + (by ? acn::kP1 : 0u);
+    const uint32_t zi = (uint32_t)(int)fz * acn::kP2 + (bz ? acn::kP2 : 0u);
+    const uint32_t h = (xi ^ yi ^ zi) & mask;
+    const float k = corner_k((ggx[3 * m] * r) * X.d1, (ggx[3 * m + 1] * r) * Y.d1, (ggx[3 * m + 2] * r) * Z.d1,
+                             bx ? X.w : X.a, by ? Y.w : Y.a, bz ? Z.w : Z.a, bx, by, bz);
+    unsafeAtomicAdd(gtable + (((int64_t)l << log2T) + h) * 2 + f, k * gout[(m * L + l) * 2 + f]);
+}
+
+// generic F: hashgrid_bwd_gen's mapping, one lane per (point, level)
+template <int INTERP>
+__global__ void __launch_bounds__(256) hashgrid_bwd_input_bwd_table_gen(const float* __restrict__ x01, int64_t M,
+                                                                        const float* __restrict__ gout,
+                                                                        const float* __restrict__ ggx, Res32 res,
+                                                                        int L, int log2T, int F,
+                                                                        float* __restrict__ gtable) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t m = gid / L;
+    const int l = (int)(gid - m * L);
+    if (m >= M) return;
+    const float r = (float)res.v[l];
+    const float sx = x01[3 * m] * r, sy = x01[3 * m + 1] * r, sz = x01[3 * m + 2] * r;
+    const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
+    float* tl = gtable + ((int64_t)l << log2T) * F;
+    const float* g = gout + (m * L + l) * F;
+    const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
+    const AxisW X = axis_w<INTERP>(sx - fx), Y = axis_w<INTERP>(sy - fy), Z = axis_w<INTERP>(sz - fz);
+    float k[8];
+    corner_ks(X, Y, Z, r, ggx[3 * m], ggx[3 * m + 1], ggx[3 * m + 2], k);
+    const uint32_t x0 = (uint32_t)(int)fx;
+    const uint32_t y0 = (uint32_t)(int)fy * acn::kP1;
+    const uint32_t z0 = (uint32_t)(int)fz * acn::kP2;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const uint32_t h = ((x0 + ((c & 1) ? 1u : 0u)) ^ (y0 + ((c & 4) ? acn::kP1 : 0u)) ^ (z0 + ((c & 2) ? acn::kP2 : 0u))) & mask;
+        float* e = tl + (int64_t)h * F;
+        for (int f = 0; f < F; ++f) unsafeAtomicAdd(e + f, k[c] * g[f]);
+    }
+}
+
 __global__ void __launch_bounds__(256) zero_f32(float* __restrict__ p, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = 0.0f;
@@ -826,6 +1104,71 @@ extern "C" int acn_hashgrid_bwd_input(const float* x01, int64_t M, const float* 
         else hipLaunchKernelGGL(hashgrid_bwd_input_gen<2>, blocks(M), block, 0, s, x01, M, grad_out, table, r, L, log2T, F, grad_x);
     }
     return acn_check_launch("acn_hashgrid_bwd_input");
+}
+
+extern "C" int acn_hashgrid_bwd_input_bwd(const float* x01, int64_t M, const float* grad_out, const float* gg_x,
+                                          const float* table, const int32_t* res, int L, int log2T, int F, int interp,
+                                          float* gg_out, float* g_x, void* stream) {
+    ACN_REQUIRE(M >= 0, "acn_hashgrid_bwd_input_bwd: M must be >= 0");
+    ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS, "acn_hashgrid_bwd_input_bwd: levels must be in [1, %d], got %d", ACN_MAX_LEVELS, L);
+    ACN_REQUIRE(log2T >= 1 && log2T <= 30, "acn_hashgrid_bwd_input_bwd: log2_hashmap_size must be in [1, 30], got %d", log2T);
+    ACN_REQUIRE(F >= 1, "acn_hashgrid_bwd_input_bwd: features_per_level must be >= 1, got %d", F);
+    ACN_REQUIRE(interp >= 0 && interp <= 2, "acn_hashgrid_bwd_input_bwd: bad interpolation %d", interp);
+    ACN_REQUIRE(res != nullptr, "acn_hashgrid_bwd_input_bwd: res is NULL");
+    if (M == 0 || (!gg_out && !g_x)) return ACN_OK;
+    ACN_REQUIRE(x01 && grad_out && gg_x && table, "acn_hashgrid_bwd_input_bwd: NULL pointer");
+    Res32 r{};
+    for (int i = 0; i < L; ++i) r.v[i] = res[i];
+    const dim3 block(256);
+    hipStream_t s = (hipStream_t)stream;
+    auto blocks = [](int64_t threads) { return dim3((unsigned)((threads + 255) / 256)); };
+    if (interp == 0) {  // the input gradient is identically 0: so are its derivatives
+        if (gg_out) hipLaunchKernelGGL(zero_f32, blocks(M * L * F), block, 0, s, gg_out, M * L * F);
+        if (g_x) hipLaunchKernelGGL(zero_f32, blocks(3 * M), block, 0, s, g_x, 3 * M);
+    } else if (F == 2 && ((uint64_t)L << (log2T + 3)) <= (1ull << 31)) {
+        const float2* g = (const float2*)grad_out;
+        const float2* t = (const float2*)table;
+        float2* gg = (float2*)gg_out;
+        if ((L & (L - 1)) == 0) {
+            if (interp == 1) hipLaunchKernelGGL((hashgrid_bwd_input_bwd_f2<1, true>), blocks(M * L), block, 0, s, x01, M, g, gg_x, t, r, L, log2T, gg, g_x);
+            else hipLaunchKernelGGL((hashgrid_bwd_input_bwd_f2<2, true>), blocks(M * L), block, 0, s, x01, M, g, gg_x, t, r, L, log2T, gg, g_x);
+        } else {
+            if (interp == 1) hipLaunchKernelGGL((hashgrid_bwd_input_bwd_f2<1, false>), blocks(M), block, 0, s, x01, M, g, gg_x, t, r, L, log2T, gg, g_x);
+            else hipLaunchKernelGGL((hashgrid_bwd_input_bwd_f2<2, false>), blocks(M), block, 0, s, x01, M, g, gg_x, t, r, L, log2T, gg, g_x);
+        }
+    } else {
+        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_input_bwd_gen<1>, blocks(M), block, 0, s, x01, M, grad_out, gg_x, table, r, L, log2T, F, gg_out, g_x);
+        else hipLaunchKernelGGL(hashgrid_bwd_input_bwd_gen<2>, blocks(M), block, 0, s, x01, M, grad_out, gg_x, table, r, L, log2T, F, gg_out, g_x);
+    }
+    return acn_check_launch("acn_hashgrid_bwd_input_bwd");
+}
+
+extern "C" int acn_hashgrid_bwd_input_bwd_table(const float* x01, int64_t M, const float* grad_out, const float* gg_x,
+                                                const int32_t* res, int L, int log2T, int F, int interp,
+                                                float* grad_table, void* stream) {
+    ACN_REQUIRE(M >= 0, "acn_hashgrid_bwd_input_bwd_table: M must be >= 0");
+    ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS, "acn_hashgrid_bwd_input_bwd_table: levels must be in [1, %d], got %d", ACN_MAX_LEVELS, L);
+    ACN_REQUIRE(log2T >= 1 && log2T <= 30, "acn_hashgrid_bwd_input_bwd_table: log2_hashmap_size must be in [1, 30], got %d", log2T);
+    ACN_REQUIRE(F >= 1, "acn_hashgrid_bwd_input_bwd_table: features_per_level must be >= 1, got %d", F);
+    ACN_REQUIRE(interp >= 0 && interp <= 2, "acn_hashgrid_bwd_input_bwd_table: bad interpolation %d", interp);
+    ACN_REQUIRE(res != nullptr, "acn_hashgrid_bwd_input_bwd_table: res is NULL");
+    if (M == 0 || interp == 0) return ACN_OK;   // Nearest: nothing depends on the table through grad_x
+    ACN_REQUIRE(x01 && grad_out && gg_x && grad_table, "acn_hashgrid_bwd_input_bwd_table: NULL pointer");
+    Res32 r{};
+    for (int i = 0; i < L; ++i) r.v[i] = res[i];
+    const dim3 block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (F == 2) {
+        const int64_t waves = ((M + 3) / 4) * L;
+        const dim3 grid((unsigned)((waves + 3) / 4));
+        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_f2<1>, grid, block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, grad_table);
+        else hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_f2<2>, grid, block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, grad_table);
+    } else {
+        const dim3 grid((unsigned)((M * L + 255) / 256));
+        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_gen<1>, grid, block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, F, grad_table);
+        else hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_gen<2>, grid, block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, F, grad_table);
+    }
+    return acn_check_launch("acn_hashgrid_bwd_input_bwd_table");
 }
 
 extern "C" int acn_sh_bwd(const float* d, int64_t M, int levels, const float* g_out, float* g_d, void* stream) {

@@ -157,12 +157,24 @@ class _HashGridFn(torch.autograd.Function):
             ctx.save_for_backward(x01)
         ctx.enc = enc
         ctx.table = table
+        # sampled here: the scope is thread-local and a CUDA backward node runs on autograd's worker thread
+        from .ray_rendering import _second_order
+        ctx.second_order = _second_order()
         return ops.hashgrid_fwd(x01, table, enc._res_host, enc.log2_hashmap_size, enc.features_per_level,
                                 enc._interp_code)
 
     @staticmethod
     def backward(ctx, g):
         if ctx.needs_input_grad[0]:
+            if ctx.second_order:
+                # the point gradient as an autograd node of its own: differentiable in (x01, g, table) when this
+                # backward is recorded, the plain kernel call when not.  The table gradient stays the first-order
+                # scatter, a constant of a recorded backward (as in second-order MAML).
+                x01, table = ctx.saved_tensors
+                gx = _HashGridInputGradFn.apply(x01, g, table, ctx.enc)
+                with torch.no_grad():
+                    gt = _HashGridFn._backward_table(ctx, g.detach())[1]
+                return gx, gt, None
             _first_order_only("HashGridEncoder")
             return _HashGridFn._backward_points(ctx, g)
         return _HashGridFn._backward_table(ctx, g)
@@ -191,6 +203,42 @@ class _HashGridFn(torch.autograd.Function):
             gt = ops.hashgrid_bwd(x01, g.contiguous(), enc._res_host, enc.log2_hashmap_size, enc.features_per_level,
                                   enc._interp_code)
         return None, gt, None
+
+
+class _HashGridInputGradFn(torch.autograd.Function):
+    """grad_x = d sum(out * g) / d x01 of the hash grid as a differentiable function of (x01, g, table): the forward
+    is _HashGridFn's point backward (ops.hashgrid_bwd_input, bit for bit), the backward its double backward
+    (ops.hashgrid_bwd_input_bwd / _table).  Only reached inside ray_rendering.second_order()."""
+
+    @staticmethod
+    def forward(ctx, x01, g, table, enc):
+        ctx.save_for_backward(x01, g, table)
+        ctx.enc = enc
+        return ops.hashgrid_bwd_input(x01, g, table, enc._res_host, enc.log2_hashmap_size, enc.features_per_level,
+                                      enc._interp_code).to(x01.dtype)
+
+    @staticmethod
+    def backward(ctx, v):
+        if torch.is_grad_enabled():
+            raise AcnError("HashGridEncoder: third-order gradients (a second-order gradient of the input gradient) "
+                           "are not implemented on the HIP path")
+        return _HashGridInputGradFn._backward(ctx, v)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, v):
+        x01, g, table = ctx.saved_tensors
+        enc = ctx.enc
+        cfg = (enc._res_host, enc.log2_hashmap_size, enc.features_per_level, enc._interp_code)
+        need_x, need_g, need_t = ctx.needs_input_grad[:3]
+        gg = gx = gt = None
+        if need_x or need_g:
+            gg, gx = ops.hashgrid_bwd_input_bwd(x01, g, v, table, *cfg, want_gg=need_g, want_gx=need_x)
+            gg = gg.to(g.dtype) if need_g else None
+            gx = gx.to(x01.dtype) if need_x else None
+        if need_t:
+            gt = ops.hashgrid_bwd_input_bwd_table(x01, g, v, *cfg).to(table.dtype)
+        return gx, gg, gt, None
 
 
 class HashGridEncoder(nn.Module):

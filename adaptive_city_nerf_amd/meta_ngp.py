@@ -11,6 +11,7 @@ marching methods (meta_ngp.py:242-443).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, List, Literal, Optional, Tuple, Union
 
@@ -241,6 +242,23 @@ class MetaNGP(MetaModule):
             return sigma
         geo = self.geo_head(h, params=self.get_subdict(params, "geo_head"))
         return {"sigma": sigma, "geo_feat": geo}
+
+    def density_and_gradient(self, x: Tensor, params: Optional[Dict[str, Tensor]] = None,
+                             create_graph: bool = False) -> Tuple[Tensor, Tensor]:
+        """(sigma (...,1), d sigma / d x (...,3)) in world coordinates: the unnormalised surface normal.
+
+        ``create_graph=True`` evaluates inside ray_rendering.second_order(): both results carry a graph to the hash
+        table, the MLP (or ``params``) and ``x``, so a loss on the gradient (eikonal, normal smoothness, orientation)
+        trains them -- the hash grid through its double-backward kernels, the MLP through the
+        composed torch chain.  trunc_exp keeps the reference's rule there: its saved clamped input is a constant of
+        the recorded backward, so the second-order terms are the reference's, term for term.  ``create_graph=False``
+        is the first-order input gradient and returns no graph."""
+        from .ray_rendering import second_order
+        with torch.enable_grad(), (second_order() if create_graph else contextlib.nullcontext()):
+            xr = x if create_graph and x.requires_grad else x.detach().requires_grad_()
+            sigma = self.density(xr, params=params)
+            (grad,) = torch.autograd.grad(sigma.sum(), xr, create_graph=create_graph)
+        return (sigma if create_graph else sigma.detach()), grad
 
     def _fused_train_ok(self, x: Tensor, params=None) -> bool:
         from .ray_rendering import _second_order

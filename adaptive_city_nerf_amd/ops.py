@@ -119,6 +119,61 @@ def hashgrid_bwd_input(x01: torch.Tensor, grad_out: torch.Tensor, table: torch.T
     return gx.view(*x01.shape[:-1], 3)
 
 
+def _bwd_input_bwd_args(x01, grad_out, gg_x, resolutions, F):
+    require_hip(x01, "HashGridEncoder")
+    assert x01.shape[-1] == 3, f"Expected (...,3), got {tuple(x01.shape)}"
+    L = len(resolutions)
+    x = _f32(x01).view(-1, 3)
+    g = _f32(grad_out).view(-1, L * F)
+    v = _f32(gg_x).view(-1, 3)
+    if g.shape[0] != x.shape[0]:
+        raise AcnError(f"grad_out must be ({x.shape[0]}, {L * F}), got {tuple(g.shape)}")
+    if v.shape[0] != x.shape[0]:
+        raise AcnError(f"gg_x must be ({x.shape[0]}, 3), got {tuple(v.shape)}")
+    return x, g, v, L, (C.c_int32 * L)(*[int(r) for r in resolutions])
+
+
+def hashgrid_bwd_input_bwd(x01: torch.Tensor, grad_out: torch.Tensor, gg_x: torch.Tensor, table: torch.Tensor,
+                           resolutions: Sequence[int], log2T: int, F: int, interp: int, want_gg: bool = True,
+                           want_gx: bool = True):
+    """Double backward of hashgrid_bwd_input, gather side (acn_hashgrid_bwd_input_bwd): with ``gg_x`` (..., 3) the
+    cotangent of the point gradient, returns (gg_out (..., L*F) | None, g_x (..., 3) | None), the derivatives of
+    sum(gg_x * hashgrid_bwd_input(x01, grad_out, table)) in ``grad_out`` and in ``x01``.  No atomics, bitwise
+    reproducible, each point's result independent of the batch around it.  Nearest gives zeros."""
+    x, g, v, L, res = _bwd_input_bwd_args(x01, grad_out, gg_x, resolutions, F)
+    tab = _f32(table)
+    if tab.shape != (L << log2T, F):
+        raise AcnError(f"hash table must be ({L << log2T}, {F}), got {tuple(tab.shape)}")
+    M = x.shape[0]
+    gg = torch.empty(M, L * F, device=x.device, dtype=torch.float32) if want_gg else None
+    gx = torch.empty(M, 3, device=x.device, dtype=torch.float32) if want_gx else None
+    check(_lib.lib().acn_hashgrid_bwd_input_bwd(ptr(x), M, ptr(g), ptr(v), ptr(tab), res, L, log2T, F, interp,
+                                                ptr(gg) if want_gg else None, ptr(gx) if want_gx else None,
+                                                stream_of(x)), "acn_hashgrid_bwd_input_bwd")
+    lead = x01.shape[:-1]
+    return (gg.view(*lead, L * F) if want_gg else None, gx.view(*lead, 3) if want_gx else None)
+
+
+def hashgrid_bwd_input_bwd_table(x01: torch.Tensor, grad_out: torch.Tensor, gg_x: torch.Tensor,
+                                 resolutions: Sequence[int], log2T: int, F: int, interp: int,
+                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Double backward of hashgrid_bwd_input, table side (acn_hashgrid_bwd_input_bwd_table): the derivative of
+    sum(gg_x * hashgrid_bwd_input(x01, grad_out, table)) in the table, (L * 2^log2T, F) fp32, scattered with float
+    atomics (into ``out``, accumulating, when given).  The sum order is not fixed and there is no sort-based
+    variant: under torch.use_deterministic_algorithms(True) this raises instead of being quietly non-deterministic."""
+    if torch.are_deterministic_algorithms_enabled():
+        raise AcnError("hashgrid_bwd_input_bwd_table: the table gradient of the second-order point gradient is a "
+                       "float-atomic scatter with no deterministic variant (torch.use_deterministic_algorithms)")
+    x, g, v, L, res = _bwd_input_bwd_args(x01, grad_out, gg_x, resolutions, F)
+    if out is not None:
+        if tuple(out.shape) != (L << log2T, F) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("hashgrid_bwd_input_bwd_table: out must be a contiguous fp32 (L * 2^log2T, F) buffer")
+    gt = out if out is not None else torch.zeros(L << log2T, F, device=x.device, dtype=torch.float32)
+    check(_lib.lib().acn_hashgrid_bwd_input_bwd_table(ptr(x), x.shape[0], ptr(g), ptr(v), res, L, log2T, F, interp,
+                                                      ptr(gt), stream_of(x)), "acn_hashgrid_bwd_input_bwd_table")
+    return gt
+
+
 def table_to_f16(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp16 copy of an fp32 tensor, round to nearest even (acn_table_to_f16), on the current stream; written into
     ``out`` (a contiguous float16 tensor of the same shape and device) when given.  The render-table shadow of

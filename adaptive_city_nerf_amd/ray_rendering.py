@@ -41,7 +41,8 @@ _GRAPH_MODE = threading.local()
 def second_order(enabled: bool = True):
     """Within this context, differentiable renders build twice-differentiable graphs (second-order
     MAML: meta_core.py:57 takes ``autograd.grad(create_graph=True)`` of the inner loss): the
-    compositing runs as torch ops instead of the HIP forward/backward pair.  Thread-local."""
+    compositing runs as torch ops instead of the HIP forward/backward pair, and a hash grid evaluated
+    here has a differentiable point gradient.  Thread-local."""
     prev = getattr(_GRAPH_MODE, "second_order", False)
     _GRAPH_MODE.second_order = bool(enabled)
     try:

@@ -124,6 +124,28 @@ int acn_hashgrid_bwd_input(const float* x01, int64_t M, const float* grad_out, c
                            const int32_t* res, int L, int log2T, int F, int interp, float* grad_x,
                            void* stream);
 
+/* Double backward of acn_hashgrid_bwd_input: with gg_x (M,3) the cotangent of grad_x, the
+ * derivatives of sum(gg_x * grad_x) in grad_out and in the points.  Per level, with u the raw weights, w = S(u),
+ * c_b the trilinear weight of corner b and D_ab = d c_b / d w_a:
+ *   k_b         = sum_a gg_x[a] * res * S'(u_a) * D_ab
+ *   gg_out[l,f] = sum_b k_b * T[b,f]
+ *   g_x[e]      = sum_l res^2 sum_b V_b (gg_x[e] S''(u_e) D_eb + sum_{a != e} gg_x[a] S'(u_a) S'(u_e) d D_ab / d w_e),
+ *                 V_b = sum_f grad_out[l,f] T[b,f]
+ * (Linear: S' = 1, S'' = 0, the cross terms only).  gg_out (M, L*F) and g_x (M,3) are overwritten; either may be
+ * NULL (not computed), both NULL is a no-op.  Nearest writes exact zeros.  No atomics, the gathers and the level
+ * order of acn_hashgrid_bwd_input: results repeat bit for bit and do not depend on M or on the other points.
+ * Any L in [1, 32], F >= 1 (checked before any HIP call); M == 0 is a no-op.                                  */
+int acn_hashgrid_bwd_input_bwd(const float* x01, int64_t M, const float* grad_out, const float* gg_x,
+                               const float* table, const int32_t* res, int L, int log2T, int F, int interp,
+                               float* gg_out, float* g_x, void* stream);
+
+/* The table side of the same double backward: grad_table[row_b, f] += k_b * grad_out[l,f], float atomics into a
+ * caller-zeroed (or accumulated) grad_table as acn_hashgrid_bwd; the sum order is not fixed.  Nearest returns
+ * without touching grad_table.                                                                                 */
+int acn_hashgrid_bwd_input_bwd_table(const float* x01, int64_t M, const float* grad_out, const float* gg_x,
+                                     const int32_t* res, int L, int log2T, int F, int interp,
+                                     float* grad_table, void* stream);
+
 /* Gradient of acn_sh_fwd in the unnormalised directions: the autograd of models/encodings.py:133-151
  * (components :27-81 differentiated as written, then n = d / max(|d|, 1e-9) as torch differentiates
  * norm and clamp_min: g_d = (g_n - n (n.g_n)) / |d| for |d| >= 1e-9, else g_n / 1e-9).

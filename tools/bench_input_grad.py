@@ -1,10 +1,14 @@
-"""Time the hash-grid input-gradient kernel (acn_hashgrid_bwd_input) against the forward (acn_hashgrid_fwd) of the
-same build, in one process: M = 1,048,576 uniform points (C2's sample count), L = 16, F = 2, log2T = 20, Linear.
+"""Time the hash-grid input-gradient kernel (acn_hashgrid_bwd_input) and its double backward
+(acn_hashgrid_bwd_input_bwd, acn_hashgrid_bwd_input_bwd_table) against the forward (acn_hashgrid_fwd)
+and the table backward (acn_hashgrid_bwd) of the same build, in one process: M = 1,048,576 uniform points (C2's
+sample count), L = 16, F = 2, log2T = 20, Linear.
 
 HIP events around every single launch, median of 20 after 5 warm-ups.  Both kernels gather the
 same 8 rows per (point, level); the bytes/s figures are over the algorithmic traffic per point: 16 levels x 8 rows x
 8 B = 1024 B of table rows, 128 B of features (written by the forward, read as grad_out by the backward) and 24 B
-of points and point gradients.  There is no gate: the forward is the yardstick.
+of points and point gradients.  There is no gate: the forward is the yardstick of the two gather kernels (the
+double backward reads grad_out and the 12-B cotangent and writes 128 B + 12 B more than the first backward; its line
+counts those), the float-atomic acn_hashgrid_bwd that of the scatter (the same 16 x 8 x 2 atomics per point).
 
 python tools/bench_input_grad.py [--interp 1|2] [--points M]
 """
@@ -56,11 +60,28 @@ def main():
                                                          st), "acn_hashgrid_fwd"))
     bwd = median_ms(lambda: check(lib().acn_hashgrid_bwd_input(ptr(x), M, ptr(g), ptr(table), r32, L, log2T, F,
                                                                a.interp, ptr(gx), st), "acn_hashgrid_bwd_input"))
+    v = torch.randn(M, 3, device=dev, generator=gen)
+    gg, gx2 = torch.empty(M, L * F, device=dev), torch.empty(M, 3, device=dev)
+    gt = torch.zeros(L << log2T, F, device=dev)     # the scatters accumulate: values grow, the work does not change
+    bwd2 = median_ms(lambda: check(lib().acn_hashgrid_bwd_input_bwd(ptr(x), M, ptr(g), ptr(v), ptr(table), r32, L, log2T,
+                                                                    F, a.interp, ptr(gg), ptr(gx2), st),
+                                   "acn_hashgrid_bwd_input_bwd"))
+    scat = median_ms(lambda: check(lib().acn_hashgrid_bwd(ptr(x), M, ptr(g), r32, L, log2T, F, a.interp, ptr(gt), st),
+                                   "acn_hashgrid_bwd"))
+    scat2 = median_ms(lambda: check(lib().acn_hashgrid_bwd_input_bwd_table(ptr(x), M, ptr(g), ptr(v), r32, L, log2T, F,
+                                                                          a.interp, ptr(gt), st),
+                                    "acn_hashgrid_bwd_input_bwd_table"))
     per_point = 1024 + 128 + 24
-    for name, ms in (("acn_hashgrid_fwd", fwd), ("acn_hashgrid_bwd_input", bwd)):
-        print(f"{name:24s} {M} pts x {L} levels, interp {a.interp}: {ms * 1e3:8.1f} us  "
-              f"{M * per_point / (ms * 1e-3) / 1e12:6.3f} TB/s algorithmic")
+    for name, ms, extra in (("acn_hashgrid_fwd", fwd, 0), ("acn_hashgrid_bwd_input", bwd, 0),
+                            ("acn_hashgrid_bwd_input_bwd", bwd2, 128 + 24)):
+        print(f"{name:32s} {M} pts x {L} levels, interp {a.interp}: {ms * 1e3:8.1f} us  "
+              f"{M * (per_point + extra) / (ms * 1e-3) / 1e12:6.3f} TB/s algorithmic")
+    for name, ms in (("acn_hashgrid_bwd", scat), ("acn_hashgrid_bwd_input_bwd_table", scat2)):
+        print(f"{name:32s} {M} pts x {L} levels, interp {a.interp}: {ms * 1e3:8.1f} us  "
+              f"{M * 1024 / (ms * 1e-3) / 1e12:6.3f} TB/s of added bytes")
     print(f"bwd_input / fwd = {bwd / fwd:.3f}")
+    print(f"bwd_input_bwd / fwd = {bwd2 / fwd:.3f}")
+    print(f"bwd_input_bwd_table / bwd = {scat2 / scat:.3f}")
 
 
 if __name__ == "__main__":
