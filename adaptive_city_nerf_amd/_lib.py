@@ -166,6 +166,9 @@ SIGNATURES = {
     "acn_mlp_train_bwd_dw_img": ([vp, vp, vp, vp, i64, vp, vp, vp, vp, vp], C.c_int),
     "acn_mlp_train_bwd_input": ([vp, vp, vp, vp, i64, vp, vp, vp, vp, vp], C.c_int),
     "acn_mlp_train_bwd_input_img": ([vp, vp, vp, vp, i64, vp, vp, vp, vp], C.c_int),
+    "acn_field_sigma_grad": ([vp, i64, i64, vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, vp, vp, f32, vp, vp, vp, vp],
+                             C.c_int),
+    "acn_normal_composite": ([vp, vp, i64, i32, vp, vp], C.c_int),
     # routed.hip
     "acn_routed_workspace_bytes": ([i64, i32], C.c_size_t),
     "acn_routed_count": ([vp, i64, i32, vp, vp, i32, vp, vp, vp, sz, vp], C.c_int),
@@ -210,6 +213,7 @@ MLP_ENTRY_POINTS = ("acn_mlp_workspace_bytes", "acn_mlp_train_fwd", "acn_mlp_tra
                     "acn_mlp_train_bwd_input_img", "acn_mlp_pairs_workspace_bytes", "acn_mlp_pack_pairs",
                     "acn_mlp_train_fwd_pairs", "acn_mlp_train_bwd_dw_pairs")
 SIGNATURES.update({n + sfx: SIGNATURES[n] for n in MLP_ENTRY_POINTS for sfx in ("_exact", "_amp")})
+SIGNATURES["acn_field_sigma_grad_exact"] = SIGNATURES["acn_field_sigma_grad"]   # evaluation only: no _amp form
 
 
 def lib():

@@ -347,6 +347,37 @@ __device__ __forceinline__ void hash_finish_x(const HashPendingX& p, float& o0, 
     hash_finish<INTERP>(h, o0, o1);
 }
 
+// Point derivative of one hash-grid level (the input-gradient kernels of encoders.hip and field_sigma_grad_kernel,
+// mlp_train.hip): v[] are the corner values folded over the features (v_corner = sum_f g_f * row_f) in hash_issue's
+// order (bit0 = x1, bit1 = z1, bit2 = y1), w the raw (unsmoothed) weights, r the level's resolution.  d/dw_z is the
+// difference of the two z-planes, d/dw_y the z-lerp of the y-differences of the x-lerps, d/dw_x the y -> z lerp of the
+// four x-differences; dw/dx = r (Linear) or r * 6 w (1 - w) (Smoothstep).
+struct LevelGrad {
+    float x, y, z;
+};
+
+template <int INTERP>
+__device__ __forceinline__ LevelGrad level_grad(const float (&v)[8], float wx, float wy, float wz, float r) {
+    float dx = r, dy = r, dz = r;
+    if (INTERP == 2) {
+        dx = r * ((6.0f * wx) * (1.0f - wx));
+        dy = r * ((6.0f * wy) * (1.0f - wy));
+        dz = r * ((6.0f * wz) * (1.0f - wz));
+        wx = (wx * wx) * (3.0f - 2.0f * wx);
+        wy = (wy * wy) * (3.0f - 2.0f * wy);
+        wz = (wz * wz) * (3.0f - 2.0f * wz);
+    }
+    const float ax = 1.0f - wx, ay = 1.0f - wy, az = 1.0f - wz;
+    const float c00 = v[0] * ax + v[1] * wx, c01 = v[2] * ax + v[3] * wx;   // c{y}{z}: the forward's x-lerps
+    const float c10 = v[4] * ax + v[5] * wx, c11 = v[6] * ax + v[7] * wx;
+    const float c0 = c00 * ay + c10 * wy, c1 = c01 * ay + c11 * wy;
+    const float d00 = v[1] - v[0], d01 = v[3] - v[2], d10 = v[5] - v[4], d11 = v[7] - v[6];
+    const float gx = (d00 * ay + d10 * wy) * az + (d01 * ay + d11 * wy) * wz;
+    const float gy = (c10 - c00) * az + (c11 - c01) * wz;
+    const float gz = c1 - c0;
+    return LevelGrad{dx * gx, dy * gy, dz * gz};
+}
+
 // The INTERP template value of the fused field also carries the table's storage format: 0 nearest, 1 linear,
 // 2 smoothstep on the fp32 table; 3 linear, 4 smoothstep on an fp16 copy of it (acn_expert.table_fmt; there is no
 // fp16 nearest).  The format is a compile-time property: one gather body per instantiation.

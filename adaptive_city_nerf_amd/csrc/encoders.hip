@@ -526,32 +526,9 @@ MergeCfg merge_cfg(int L, int log2T, int levels = ACN_HASH_BWD_MERGE) {
 // No atomics: a point's level terms are summed in a fixed order that depends on nothing but L -- an xor-shuffle
 // tree over the point's L adjacent lanes when L is a power of two (TREE: one lane per (point, level), as the
 // forward), else one lane per point adding levels 0 .. L-1 in turn.
-struct LevelGrad {
-    float x, y, z;
-};
-
-// v[]: the folded corner values in hash_issue's order (bit0 = x1, bit1 = z1, bit2 = y1); w: the raw weights
-template <int INTERP>
-__device__ __forceinline__ LevelGrad level_grad(const float (&v)[8], float wx, float wy, float wz, float r) {
-    float dx = r, dy = r, dz = r;
-    if (INTERP == 2) {
-        dx = r * ((6.0f * wx) * (1.0f - wx));
-        dy = r * ((6.0f * wy) * (1.0f - wy));
-        dz = r * ((6.0f * wz) * (1.0f - wz));
-        wx = (wx * wx) * (3.0f - 2.0f * wx);
-        wy = (wy * wy) * (3.0f - 2.0f * wy);
-        wz = (wz * wz) * (3.0f - 2.0f * wz);
-    }
-    const float ax = 1.0f - wx, ay = 1.0f - wy, az = 1.0f - wz;
-    const float c00 = v[0] * ax + v[1] * wx, c01 = v[2] * ax + v[3] * wx;   // c{y}{z}: the forward's x-lerps
-    const float c10 = v[4] * ax + v[5] * wx, c11 = v[6] * ax + v[7] * wx;
-    const float c0 = c00 * ay + c10 * wy, c1 = c01 * ay + c11 * wy;
-    const float d00 = v[1] - v[0], d01 = v[3] - v[2], d10 = v[5] - v[4], d11 = v[7] - v[6];
-    const float gx = (d00 * ay + d10 * wy) * az + (d01 * ay + d11 * wy) * wz;
-    const float gy = (c10 - c00) * az + (c11 - c01) * wz;
-    const float gz = c1 - c0;
-    return LevelGrad{dx * gx, dy * gy, dz * gz};
-}
+// level_grad (acn_device.h) differentiates one level's trilinear form; field_sigma_grad_kernel (mlp_train.hip) shares it.
+using acn::LevelGrad;
+using acn::level_grad;
 
 template <int INTERP>
 __device__ __forceinline__ LevelGrad level_grad_f2(__amdgpu_buffer_rsrc_t rs, int l, int log2T, uint32_t mask,

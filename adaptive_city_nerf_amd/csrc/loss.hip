@@ -7,6 +7,8 @@
 // sums, one fixed reduction order: deterministic) and one elementwise launch backward.
 // Float semantics follow the torch ops: scalars as float (12.92f, 0.055f, 1.055f, 0.04045f), powf with
 // the float exponent, clamps that pass NaN through, and mse_loss_backward's double `2 / numel` factor.
+// Also here, as the other small per-ray reduction: acn_normal_composite, the weighted sum of the samples' unit
+// normals of a rendered normal map.
 #include "acn_device.h"
 #include "acn_internal.h"
 
@@ -121,6 +123,30 @@ __global__ void __launch_bounds__(256) mse_linear_bwd_kernel(const float* __rest
     g_pred[e] = (p >= 0.0f && p <= 1.0f) ? g : 0.0f;
 }
 
+// Normal map compositing (acn_normal_composite): n = sum_s w_s * (-g_s / max(|g_s|, 1e-9)) per ray, g_s the density
+// gradient of sample s (acn_field_sigma_grad).  One lane per ray; every term in fp32 (norm3, one division and one
+// product per component), accumulated in float64 in sample order and rounded once: deterministic, and a zero
+// gradient (a gated sample) adds exactly 0.
+__global__ void __launch_bounds__(256) normal_composite_kernel(const float* __restrict__ grad,
+                                                               const float* __restrict__ weights, int64_t N, int S,
+                                                               float* __restrict__ normal) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const float* g = grad + n * S * 3;
+    const float* w = weights + n * S;
+    double ax = 0.0, ay = 0.0, az = 0.0;
+    for (int s = 0; s < S; ++s) {
+        const float gx = g[3 * s], gy = g[3 * s + 1], gz = g[3 * s + 2], ws = w[s];
+        const float d = acn::clamp_min_nan(acn::norm3(gx, gy, gz), 1e-9f);
+        ax += (double)(ws * (-gx / d));
+        ay += (double)(ws * (-gy / d));
+        az += (double)(ws * (-gz / d));
+    }
+    normal[3 * n] = (float)ax;
+    normal[3 * n + 1] = (float)ay;
+    normal[3 * n + 2] = (float)az;
+}
+
 }  // namespace
 
 extern "C" int acn_mse_linear_fwd(const float* pred, const float* gt, int64_t n, float* loss, void* stream) {
@@ -150,4 +176,14 @@ extern "C" int acn_mse_linear_bwd(const float* pred, const float* gt, int64_t n,
     hipLaunchKernelGGL(mse_linear_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        pred, gt, n, g_loss, g_pred);
     return acn_check_launch("acn_mse_linear_bwd");
+}
+
+extern "C" int acn_normal_composite(const float* grad, const float* weights, int64_t N, int S, float* normal,
+                                    void* stream) {
+    ACN_REQUIRE(N >= 0 && S >= 1, "acn_normal_composite: N must be >= 0 and S >= 1 (got %lld, %d)", (long long)N, S);
+    if (N == 0) return ACN_OK;
+    ACN_REQUIRE(grad && weights && normal, "acn_normal_composite: NULL pointer");
+    hipLaunchKernelGGL(normal_composite_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       grad, weights, N, S, normal);
+    return acn_check_launch("acn_normal_composite");
 }

@@ -10,7 +10,9 @@
 //                      (after the ReLU / sigmoid / trunc_exp derivative);
 // then one GEMM per layer on the caller's side gives [dW | db] = dY^T . [X | 1] (large-K GEMMs);
 //   acn_mlp_train_bwd_dw: the fused backward (forward re-run in registers, [dW | db] on MFMA, no saved activations);
-//   acn_mlp_train_bwd_input: the input gradients alone (dL/dh0, dL/dsh) for frozen weights, one launch.
+//   acn_mlp_train_bwd_input: the input gradients alone (dL/dh0, dL/dsh) for frozen weights, one launch;
+//   acn_field_sigma_grad: density and its world-space gradient for evaluation (hash gather, sigma branch forward and
+//                      backward, contraction with the corner rows) in one launch, nothing else written.
 //
 // Execution: one wave per 32-sample tile, lanes (sample j = lane & 31, half h = lane >> 5).  Every
 // layer is Y^T = W . X^T on v_mfma_f32_32x32x2_f32 (exact fp32 fma chains) with the layer input in the
@@ -2079,6 +2081,193 @@ __global__ void __launch_bounds__(256) mlp_bwd_input_kernel(const float* __restr
     }
 }
 
+#if !ACN_TRAIN_AMP
+// ---------------------------------------------------------------------------------------------
+// Density and its world-space gradient in one launch (acn_field_sigma_grad): sigma = trunc_exp(sigma_head(trunk(
+// hash(x01)))) and d sigma / d p of MetaNGP.density for p (M, 3), with nothing but (sigma, grad) written.  One wave
+// per 32-sample tile.  Lane (j, h) gathers the eight levels whose features it holds in the MFMA operand layout
+// (register pair 2i, 2i + 1 = level 4 (i >> 1) + 2h + (i & 1), features rho(2i, h), rho(2i + 1, h)) straight into X0,
+// runs the sigma branch forward and backward on the layers of mlp_bwd_input_kernel (the head's 32 padded rows, so
+// the sums are those of the fwd -> bwd_input chain with gout = e_sigma), and contracts the returned dL/dh0 of those
+// same eight levels with their corner rows, gathered a second time (level_grad, as hashgrid_bwd_input_f2).  The
+// sixteen level terms are added in that kernel's xor-tree order -- pairs inside a lane, then across the two lane halves,
+// then quads and octets -- so the result equals the four-launch chain bit for bit.  After the weight staging there is
+// no barrier, no LDS write and no atomic; every row depends on its own sample only.
+struct SigmaGradArgs {
+    const float* x;
+    int64_t M, ld;
+    const float* table;
+    int32_t res[16];
+    int32_t log2T;
+    float amin[3], ext[3];
+    float lo, hi;
+    const float* gate;
+    float gate_min;
+    float* sigma;
+    float* grad;
+};
+
+// Gathers in flight per lane: the renders' depth (ACN_HASH_DEPTH, render.hip), 3 levels = 24 buffer loads, held by
+// scheduling barriers.  Left to itself hipcc issued all 64 loads of a gather pass at once, the ceiling of the 6-bit
+// vmcnt counter, and at 1 M points a few tiles per call then returned wrong, run-to-run different gradients in rows
+// 16..31 (the shape of 4l's wrong gathers).
+constexpr int SG_DEPTH = 3;
+
+// gather step i of the lane's point: level 4 (i >> 1) + 2h + (i & 1) (features rho(2i, h), rho(2i + 1, h))
+template <int INTERP>
+__device__ __forceinline__ float sg_issue(__amdgpu_buffer_rsrc_t rs, const SigmaGradArgs& a, int i, int h, uint32_t mask,
+                                          float x0, float x1, float x2, acn::HashPendingX& p) {
+    const int l0 = 4 * (i >> 1) + (i & 1);       // the level of half 0; half 1 holds l0 + 2
+    const float r = (float)(h ? a.res[l0 + 2] : a.res[l0]);
+    acn::hash_issue_x<INTERP>(rs, (uint32_t)(l0 + 2 * h) << (a.log2T + 3), x0 * r, x1 * r, x2 * r, mask, p);
+    return r;
+}
+
+#ifndef ACN_SG_WAVES
+#define ACN_SG_WAVES 2   // waves per SIMD the register budget is held to: two 4-wave blocks (72 KB weight image each) per CU
+#endif
+template <int INTERP>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACN_SG_WAVES, ACN_SG_WAVES)))
+field_sigma_grad_kernel(const float* __restrict__ img, SigmaGradArgs a) {
+    __shared__ __attribute__((aligned(16))) float Wl[L_FLOATS];
+    stage_weights(img, Wl);
+    __syncthreads();
+    const int lane0 = threadIdx.x & 63, j = lane0 & 31, h0 = lane0 >> 5;
+    const uint32_t mask = (1u << a.log2T) - 1u;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)a.table, (short)0, (int)(16u << (a.log2T + 3)), 0x00020000);
+    const int64_t ntiles = (a.M + 31) / 32;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+        const int64_t m = tile * 32 + j;
+        const bool ok = m < a.M;
+        bool gated = false;
+        if (a.gate) {
+            gated = ok && a.gate[m] <= a.gate_min;
+            if (__ballot(ok && !gated) == 0ull) {   // wave-uniform: nothing live in this tile, no gather
+                if (ok && h0 == 0) {
+                    a.sigma[m] = 0.0f;
+                    a.grad[3 * m] = 0.0f;
+                    a.grad[3 * m + 1] = 0.0f;
+                    a.grad[3 * m + 2] = 0.0f;
+                }
+                continue;
+            }
+        }
+        const float* W = Wl + opaque_s(0);   // as mlp_fwd_kernel: the LDS weight reads stay inside the tile loop
+        const int lane = opaque_v(lane0), h = lane >> 5;
+        // unit coordinates (field_tile's division and clamp); a NaN coordinate stays NaN through clamp_nan, so the
+        // sample gathers at the box corner instead and enters the tile as zero features
+        const float* px = a.x + (ok ? m : 0) * a.ld;
+        const float u0 = (px[0] - a.amin[0]) / a.ext[0], u1 = (px[1] - a.amin[1]) / a.ext[1],
+                    u2 = (px[2] - a.amin[2]) / a.ext[2];
+        float x0 = acn::clamp_nan(u0, a.lo, a.hi), x1 = acn::clamp_nan(u1, a.lo, a.hi), x2 = acn::clamp_nan(u2, a.lo, a.hi);
+        const bool fin = x0 == x0 && x1 == x1 && x2 == x2;
+        const bool feed = ok && fin;
+        if (!fin) { x0 = a.lo; x1 = a.lo; x2 = a.lo; }
+        f32x16 A1[2], A2[2];
+        float sig;
+        {
+            f32x16 X0[1], Hd[1];
+            {
+                acn::HashPendingX p[SG_DEPTH];
+#pragma unroll
+                for (int i = 0; i < SG_DEPTH - 1; ++i) sg_issue<INTERP>(rs, a, i, h, mask, x0, x1, x2, p[i]);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    if (i + SG_DEPTH - 1 < 8)
+                        sg_issue<INTERP>(rs, a, i + SG_DEPTH - 1, h, mask, x0, x1, x2, p[(i + SG_DEPTH - 1) % SG_DEPTH]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    float o0, o1;
+                    acn::hash_finish_x<INTERP>(p[i % SG_DEPTH], o0, o1);
+                    X0[0][2 * i] = feed ? o0 : 0.0f;
+                    X0[0][2 * i + 1] = feed ? o1 : 0.0f;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            fwd_layer<2, 1, 64>(W + L_W0, S32, W + L_B0, X0, A1, lane);
+            relu<2>(A1);
+            fwd_layer<2, 2, 64>(W + L_W1, S64, W + L_B1, A1, A2, lane);
+            relu<2>(A2);
+            fwd_layer<1, 2, 32>(W + L_WH, S64, W + L_BH, A2, Hd, lane);
+            sig = out_sigma(Hd[0][7]);   // row 15 = sigma head (lane half 1, reg 7)
+        }
+        // d sigma / d s = sigma (TruncExp's rule, also where s was clamped): the head gradient is e_15 * sigma
+        f32x16 dHd[1], GH[1];
+        dHd[0] = 0.0f;
+        dHd[0][7] = (ok && h == 1) ? grad_sigma(1.0f, sig) : 0.0f;
+        {
+            f32x16 GA2[2], GA1[2];
+            bwd_layer<2, 1, 16, 32>(W + L_WH, S64, dHd, GA2, lane);
+            relu_mask<2>(GA2, A2);
+            bwd_layer<2, 2, 64, 64>(W + L_W1, S64, GA2, GA1, lane);
+            relu_mask<2>(GA1, A1);
+            bwd_layer<1, 2, 64, 64>(W + L_W0, S32, GA1, GH, lane);
+        }
+        // contraction: the lane's eight level terms, pairs first (levels 4q + 2h, 4q + 2h + 1)
+        float pxs[4], pys[4], pzs[4];
+        {
+            acn::HashPendingX p[SG_DEPTH];
+            float rr[SG_DEPTH];
+            acn::LevelGrad tp{0.0f, 0.0f, 0.0f};
+            // the same unit point behind an opaque copy: the pass recomputes its cells, weights and row offsets
+            // instead of holding the first pass's (~80 registers) across the layers
+            float y0 = x0, y1 = x1, y2 = x2;
+            asm volatile("" : "+v"(y0), "+v"(y1), "+v"(y2));
+            __builtin_amdgcn_sched_barrier(0);   // the second pass's gathers start here, not above the layers
+#pragma unroll
+            for (int i = 0; i < SG_DEPTH - 1; ++i) rr[i] = sg_issue<INTERP>(rs, a, i, h, mask, y0, y1, y2, p[i]);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (i + SG_DEPTH - 1 < 8)
+                    rr[(i + SG_DEPTH - 1) % SG_DEPTH] =
+                        sg_issue<INTERP>(rs, a, i + SG_DEPTH - 1, h, mask, y0, y1, y2, p[(i + SG_DEPTH - 1) % SG_DEPTH]);
+                __builtin_amdgcn_sched_barrier(0);
+                float2 f[8];
+                acn::hash_rows_x(p[i % SG_DEPTH], f);
+                const float g0 = GH[0][2 * i], g1 = GH[0][2 * i + 1], r = rr[i % SG_DEPTH];
+                float v[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) v[c] = g0 * f[c].x + g1 * f[c].y;
+                const float sx = y0 * r, sy = y1 * r, sz = y2 * r;
+                const acn::LevelGrad t = acn::level_grad<INTERP>(v, sx - floorf(sx), sy - floorf(sy), sz - floorf(sz), r);
+                if (i & 1) {
+                    pxs[i >> 1] = tp.x + t.x;
+                    pys[i >> 1] = tp.y + t.y;
+                    pzs[i >> 1] = tp.z + t.z;
+                } else {
+                    tp = t;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // ... then the other lane half's pair (levels 4q .. 4q + 3), the quads and the octets: hashgrid_bwd_input_f2's tree
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            pxs[q] += __shfl_xor(pxs[q], 32);
+            pys[q] += __shfl_xor(pys[q], 32);
+            pzs[q] += __shfl_xor(pzs[q], 32);
+        }
+        const float gx = (pxs[0] + pxs[1]) + (pxs[2] + pxs[3]);
+        const float gy = (pys[0] + pys[1]) + (pys[2] + pys[3]);
+        const float gz = (pzs[0] + pzs[1]) + (pzs[2] + pzs[3]);
+        const float sg = __shfl_xor(sig, 32);   // half 0 writes; sigma lives in half 1
+        if (ok && h == 0) {
+            // torch's clamp backward passes the gradient where the unclamped value lies in [lo, hi]
+            const float k0 = (u0 >= a.lo && u0 <= a.hi) ? 1.0f / a.ext[0] : 0.0f;
+            const float k1 = (u1 >= a.lo && u1 <= a.hi) ? 1.0f / a.ext[1] : 0.0f;
+            const float k2 = (u2 >= a.lo && u2 <= a.hi) ? 1.0f / a.ext[2] : 0.0f;
+            const float nanv = __builtin_nanf("");
+            a.sigma[m] = gated ? 0.0f : (fin ? sg : nanv);
+            a.grad[3 * m] = gated ? 0.0f : (fin ? k0 * gx : nanv);
+            a.grad[3 * m + 1] = gated ? 0.0f : (fin ? k1 * gy : nanv);
+            a.grad[3 * m + 2] = gated ? 0.0f : (fin ? k2 * gz : nanv);
+        }
+    }
+}
+#endif
+
 MlpPtrs ptrs(const acn_mlp* w) {
     return MlpPtrs{w->w0, w->b0, w->w1, w->b1, w->wsh, w->bsh, w->wg, w->bg,
                    w->wc0, w->bc0, w->wc1, w->bc1, w->wc2, w->bc2};
@@ -2205,6 +2394,44 @@ extern "C" int ACN_MLP_API(acn_mlp_train_bwd_input_img)(const float* h0, const f
                        gout, M, gh0, gsh);
     return acn_check_launch("acn_mlp_train_bwd_input_img");
 }
+
+#if !ACN_TRAIN_AMP
+// density + world-space density gradient in one launch (field_sigma_grad_kernel); workspace: acn_mlp_workspace_bytes()
+extern "C" int ACN_MLP_API(acn_field_sigma_grad)(const float* x, int64_t M, int64_t ld, const float* table,
+                                                 const int32_t* res, int L, int log2T, int F, int interp,
+                                                 const float* aabb_min, const float* aabb_extent, float lo, float hi,
+                                                 const acn_mlp* w, const float* gate, float gate_min, float* sigma,
+                                                 float* grad, void* workspace, void* stream) {
+    ACN_REQUIRE(M >= 0 && ld >= 3, "acn_field_sigma_grad: M must be >= 0 and ld >= 3 (got %lld, %lld)", (long long)M,
+                (long long)ld);
+    ACN_REQUIRE(interp >= 0 && interp <= 2, "acn_field_sigma_grad: bad interpolation %d", interp);
+    if (interp == 0)
+        return acn_set_error(ACN_ERR_UNSUPPORTED, "acn_field_sigma_grad: Nearest interpolation has no point gradient "
+                                                  "(Linear or Smoothstep)");
+    if (F != 2 || L != 16)
+        return acn_set_error(ACN_ERR_UNSUPPORTED, "acn_field_sigma_grad: the fused kernel implements 16*2 hash "
+                                                  "features (L = 16, F = 2), got L = %d, F = %d", L, F);
+    ACN_REQUIRE(log2T >= 1, "acn_field_sigma_grad: log2_hashmap_size must be >= 1, got %d", log2T);
+    if (log2T > 24)
+        return acn_set_error(ACN_ERR_UNSUPPORTED, "acn_field_sigma_grad: a table of log2_hashmap_size %d exceeds 2 GiB "
+                                                  "(32-bit gather offsets)", log2T);
+    ACN_REQUIRE(res && aabb_min && aabb_extent && w && workspace, "acn_field_sigma_grad: NULL argument");
+    if (M == 0) return ACN_OK;
+    ACN_REQUIRE(x && table && sigma && grad, "acn_field_sigma_grad: NULL pointer");
+    SigmaGradArgs a{};
+    a.x = x; a.M = M; a.ld = ld; a.table = table; a.log2T = log2T;
+    for (int l = 0; l < 16; ++l) a.res[l] = res[l];
+    for (int c = 0; c < 3; ++c) { a.amin[c] = aabb_min[c]; a.ext[c] = aabb_extent[c]; }
+    a.lo = lo; a.hi = hi; a.gate = gate; a.gate_min = gate_min; a.sigma = sigma; a.grad = grad;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(mlp_pack_kernel, dim3((L_FLOATS + 255) / 256), dim3(256), 0, s, ptrs(w), (float*)workspace);
+    if (interp == 1)
+        hipLaunchKernelGGL(field_sigma_grad_kernel<1>, dim3(grid_for(M)), dim3(256), 0, s, (const float*)workspace, a);
+    else
+        hipLaunchKernelGGL(field_sigma_grad_kernel<2>, dim3(grid_for(M)), dim3(256), 0, s, (const float*)workspace, a);
+    return acn_check_launch("acn_field_sigma_grad");
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // routed pair lists

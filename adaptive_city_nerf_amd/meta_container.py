@@ -204,6 +204,51 @@ class MetaContainer(MetaModule):
                 sig.index_copy_(0, sel, s)
         return sig
 
+    @torch.no_grad()
+    def sigma_gradient(self, xyz: torch.Tensor, params: Optional[OrderedDict] = None,
+                       active_module: Optional[int] = None, gate: Optional[torch.Tensor] = None,
+                       gate_min: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(sigma (N,), d sigma / d xyz (N,3)) of ``density`` without a graph: every expert through
+        MetaNGP.sigma_gradient (one fused launch per expert).  Hard routing partitions the points as ``density`` does;
+        soft routing returns sum_k w_k grad(sigma_k) + sum_k sigma_k grad(w_k), the second term from one autograd pass
+        through the differentiable weights (_soft_weights on the routing kernel's mask).  ``gate`` (N,): samples with
+        gate <= gate_min return zeros."""
+        assert xyz.dim() == 2 and xyz.shape[-1] == 3, "xyz must be (N,3)"
+        sub_params = self._sub_params(params)
+        xyz = xyz.detach()
+        if active_module is not None:
+            s, g = self.submodules[active_module].sigma_gradient(xyz, params=sub_params[active_module], gate=gate,
+                                                                 gate_min=gate_min)
+            return s.squeeze(-1), g
+        weights, hard = self._routing(xyz)
+        N, K = xyz.shape[0], len(self.submodules)
+        sig = xyz.new_zeros(N, dtype=torch.float32)
+        grad = xyz.new_zeros(N, 3, dtype=torch.float32)
+        sig_k = xyz.new_zeros(N, K, dtype=torch.float32) if weights is not None else None
+        for k, sub in enumerate(self.submodules):
+            sel = ((weights[:, k] > 0) if weights is not None else (hard == k)).nonzero(as_tuple=False).squeeze(1)
+            if sel.numel() == 0:
+                continue
+            s, g = sub.sigma_gradient(xyz.index_select(0, sel), params=sub_params[k],
+                                      gate=None if gate is None else gate.reshape(-1).index_select(0, sel),
+                                      gate_min=gate_min)
+            s = s.squeeze(-1)
+            if weights is not None:
+                wk = weights[:, k].index_select(0, sel)
+                sig.index_add_(0, sel, s * wk)
+                grad.index_add_(0, sel, g * wk.unsqueeze(1))
+                sig_k[:, k].index_copy_(0, sel, s)
+            else:
+                sig.index_copy_(0, sel, s)
+                grad.index_copy_(0, sel, g)
+        if weights is not None:
+            with torch.enable_grad():
+                x = xyz.to(self.centroids.device).clone().requires_grad_()
+                w = self._soft_weights(x, weights > 0)
+                (gw,) = torch.autograd.grad((w * sig_k).sum(), x)
+            grad = grad + gw.to(grad.dtype)
+        return sig, grad
+
     def forward(self, x: torch.Tensor, params: Optional[OrderedDict] = None,
                 active_module: Optional[int] = None) -> torch.Tensor:
         """Routed forward (:275-343): x (N, D>=6) -> (N, 4) [rgb, sigma]."""

@@ -252,13 +252,35 @@ class MetaNGP(MetaModule):
         trains them -- the hash grid through its double-backward kernels, the MLP through the
         composed torch chain.  trunc_exp keeps the reference's rule there: its saved clamped input is a constant of
         the recorded backward, so the second-order terms are the reference's, term for term.  ``create_graph=False``
-        is the first-order input gradient and returns no graph."""
+        is the first-order input gradient and returns no graph; ``sigma_gradient`` returns the same pair from one
+        fused launch, without autograd."""
         from .ray_rendering import second_order
         with torch.enable_grad(), (second_order() if create_graph else contextlib.nullcontext()):
             xr = x if create_graph and x.requires_grad else x.detach().requires_grad_()
             sigma = self.density(xr, params=params)
             (grad,) = torch.autograd.grad(sigma.sum(), xr, create_graph=create_graph)
         return (sigma if create_graph else sigma.detach()), grad
+
+    @torch.no_grad()
+    def sigma_gradient(self, x: Tensor, params: Optional[Dict[str, Tensor]] = None, *, gate: Optional[Tensor] = None,
+                       gate_min: float = 0.0) -> Tuple[Tensor, Tensor]:
+        """(sigma (...,1), d sigma / d x (...,3)) without a graph: the evaluation form of ``density_and_gradient``
+        (normal maps, sphere tracing, sampling along the gradient).  One fused launch (ops.field_sigma_grad) on the
+        fp32 parameter table, whatever set_render_table_dtype selected, with the fast weights of ``params``.
+        ``gate`` (...): samples with gate <= gate_min return zeros without being evaluated where a whole 32-sample
+        tile is gated.  Where the kernel does not apply (CPU tensors, a configuration the fused field does not
+        implement, Nearest interpolation) the result is density_and_gradient(create_graph=False), gated likewise."""
+        if x.is_cuda and self._fusable and self.xyz_encoder._interp_code != 0:
+            flat = x.detach().reshape(-1, 3)
+            from .ray_rendering import ENC_EPS   # enc_eps, known on the host: no device read per call
+            sig, grad = ops.field_sigma_grad(flat, self.expert_spec(params), gate=None if gate is None else
+                                             gate.detach().reshape(-1), gate_min=gate_min, eps=ENC_EPS)
+            return sig.view(*x.shape[:-1], 1), grad.view(*x.shape[:-1], 3)
+        sig, grad = self.density_and_gradient(x, params=params, create_graph=False)
+        if gate is not None:
+            off = gate.detach().reshape(*x.shape[:-1], 1) <= gate_min
+            sig, grad = sig.masked_fill(off, 0.0), grad.masked_fill(off, 0.0)
+        return sig, grad
 
     def _fused_train_ok(self, x: Tensor, params=None) -> bool:
         from .ray_rendering import _second_order

@@ -812,6 +812,64 @@ def mlp_train_bwd_input(h0: torch.Tensor, sh: torch.Tensor, out: torch.Tensor, g
     return gh, gs
 
 
+def field_sigma_grad(x: torch.Tensor, spec: ExpertSpec, *, gate: Optional[torch.Tensor] = None, gate_min: float = 0.0,
+                     precision: Optional[str] = None, eps: float = 1e-6):
+    """(sigma (M,), d sigma / d x (M, 3)) of one expert at the world points ``x`` (M, D >= 3; columns 0:3 are read)
+    in one launch (acn_field_sigma_grad): hash gather, sigma trunk and head forward and backward on the MFMA and
+    the contraction with the corner rows, nothing else written.  Evaluation only (no autograd).  ``gate`` (M,):
+    samples with gate <= gate_min return zeros, a tile of 32 such samples is skipped, the others' bits do not
+    depend on the gate.  ``precision`` follows TRAIN_MLP_PRECISION ("amp" uses the fp16x3 kernel); ``eps`` is
+    MetaNGP.enc_eps.  fp32 table, L = 16, F = 2, Linear / Smoothstep; anything else raises."""
+    require_hip(x, "field_sigma_grad")
+    if x.dim() != 2 or x.shape[1] < 3:
+        raise AcnError(f"field_sigma_grad: x must be (M, D >= 3), got {tuple(x.shape)}")
+    s = spec.s
+    if s.table_fmt != _lib.ACN_TABLE_F32:
+        raise AcnError("field_sigma_grad: fp32 tables only (the spec holds an fp16 render table)")
+    precision = precision or TRAIN_MLP_PRECISION
+    if precision not in _MLP_SUFFIX:
+        raise ValueError(f"train MLP precision must be one of {sorted(_MLP_SUFFIX)}, got {precision!r}")
+    if precision == "amp":
+        precision = "fp16x3"
+    xx = _f32(x)
+    M = xx.shape[0]
+    g = None
+    if gate is not None:
+        g = _f32(gate).reshape(-1)
+        if g.shape[0] != M or g.device != xx.device:
+            raise AcnError(f"field_sigma_grad: gate must hold {M} values on the points' device, got {tuple(gate.shape)}")
+    sigma = torch.empty(M, device=xx.device, dtype=torch.float32)
+    grad = torch.empty(M, 3, device=xx.device, dtype=torch.float32)
+    w = _mlp_struct(spec.keep[1:15])
+    wsp = torch.empty(int(mlp_fn("acn_mlp_workspace_bytes", precision)()), dtype=torch.uint8, device=xx.device)
+    import numpy as np
+    lo = np.float32(eps)
+    hi = np.float32(1.0) - lo
+    check(mlp_fn("acn_field_sigma_grad", precision)(
+        ptr(xx), M, xx.shape[1], s.table, C.cast(s.res, C.c_void_p), s.L, s.log2T, s.F, s.interp,
+        C.cast(s.aabb_min, C.c_void_p), C.cast(s.aabb_extent, C.c_void_p), C.c_float(lo), C.c_float(hi), C.byref(w),
+        ptr(g), C.c_float(gate_min), ptr(sigma), ptr(grad), ptr(wsp), stream_of(xx)), "acn_field_sigma_grad")
+    return sigma, grad
+
+
+def normal_composite(grad: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """(N, 3) = sum_s weights[n, s] * (-grad[n, s] / max(|grad[n, s]|, 1e-9)) (acn_normal_composite): the weighted
+    sum of the samples' unit normals, terms in fp32, accumulated in float64 in sample order.  ``grad`` is (N*S, 3)
+    or (N, S, 3), ``weights`` (N, S).  A zero gradient adds exactly 0."""
+    require_hip(weights, "normal_composite")
+    wv = _f32(weights)
+    if wv.dim() != 2 or wv.shape[1] < 1:
+        raise AcnError(f"normal_composite: weights must be (N, S >= 1), got {tuple(weights.shape)}")
+    N, S = wv.shape
+    gv = _f32(grad).reshape(-1, 3)
+    if gv.shape[0] != N * S or gv.device != wv.device:
+        raise AcnError(f"normal_composite: grad must be ({N * S}, 3) on the weights' device, got {tuple(grad.shape)}")
+    out = torch.empty(N, 3, device=wv.device, dtype=torch.float32)
+    check(_lib.lib().acn_normal_composite(ptr(gv), ptr(wv), N, int(S), ptr(out), stream_of(wv)),
+          "acn_normal_composite")
+    return out
+
+
 def sample_stratified(rays: torch.Tensor, S: int, jitter: Optional[torch.Tensor], aabb_min, aabb_extent,
                       eps: float):
     """Training-path sampler (acn_sample_stratified): t_vals (N,S), x01 (N*S,3) in the expert's unit box

@@ -665,6 +665,70 @@ def render_rays(model, rays, *args, **kwargs):
 
 
 @torch.no_grad()
+def render_normals(model, rays: Tensor, ray_samples: int, params=None, active_module: Optional[int] = None,
+                   bg_color_default: str = "white", min_weight: float = 0.0, chunk_rays: int = 8192,
+                   normalize: bool = True):
+    """Rendered normals of the stratified (eval) render: normal (N,3), rgb (N,3), depth (N,), acc (N,).
+
+    normal = sum_s w_s * (-grad sigma / |grad sigma|) at the render's own samples, w the compositing weights.  Per
+    chunk of ``chunk_rays`` rays: the fused stratified render with weights, the sample points o + d t of
+    stratified_t_vals(randomized=False), the model's ``sigma_gradient`` gated by the weights (samples with
+    w <= min_weight are not evaluated: each dropped term has norm <= its weight) and ops.normal_composite.
+    ``normalize``: the final F.normalize (a zero vector, e.g. a ray that hits nothing, stays zero).  Evaluation
+    only: the jittered samples of a model in training mode are not reproducible here, so it raises."""
+    if model.training:
+        raise ops.AcnError("render_normals renders the evaluation samples (model.eval()); a model in training mode "
+                           "draws jittered samples")
+    N, S = rays.shape[0], int(ray_samples)
+    normal = rays.new_zeros(N, 3, dtype=torch.float32)
+    outs = []
+    for a in range(0, N, max(1, int(chunk_rays))):
+        r = rays[a:a + chunk_rays]
+        rgb, depth, w, acc = render_rays_stratified(model, r, S, params=params, active_module=active_module,
+                                                    bg_color_default=bg_color_default)
+        t = stratified_t_vals(r[:, 6], r[:, 7], S, randomized=False)
+        pts = (r[:, None, :3] + r[:, None, 3:6] * t.unsqueeze(-1)).reshape(-1, 3)
+        gate = w.reshape(-1)
+        if isinstance(model, MetaContainer):
+            _, g = model.sigma_gradient(pts, params=params, active_module=active_module, gate=gate, gate_min=min_weight)
+        else:
+            _, g = model.sigma_gradient(pts, params=params, gate=gate, gate_min=min_weight)
+        normal[a:a + r.shape[0]] = ops.normal_composite(g, w) if r.is_cuda else _normal_composite_torch(g, w)
+        outs.append((rgb, depth, acc))
+    if normalize:
+        normal = torch.nn.functional.normalize(normal, dim=-1)
+    if len(outs) == 1:
+        rgb, depth, acc = outs[0]
+    else:
+        rgb, depth, acc = (torch.cat([o[i] for o in outs], 0) if outs else rays.new_zeros(0) for i in range(3))
+    return normal, rgb, depth, acc
+
+
+def _normal_composite_torch(grad: Tensor, weights: Tensor) -> Tensor:
+    """ops.normal_composite as torch ops (CPU models): fp32 terms, float64 sum over the samples."""
+    N, S = weights.shape
+    g = grad.reshape(N, S, 3).float()
+    d = g.norm(dim=-1, keepdim=True).clamp_min(1e-9)
+    return (weights.float().unsqueeze(-1) * (-g / d)).double().sum(1).float()
+
+
+@torch.no_grad()
+def render_normal_image(model, *, H: int, W: int, fx: float, fy: float, cx: float, cy: float, c2w: Tensor, scene_box,
+                        params=None, active_module: Optional[int] = None, ray_samples: int = 64,
+                        bg_color_default: str = "white", center_pixels: bool = True, min_weight: float = 0.0,
+                        chunk_rays: int = 8192, normalize: bool = True):
+    """Full-frame normal map, the companion of render_image: ((H,W,3) normals, (H,W,3) rgb clamped to [0,1],
+    depth (H*W,), acc (H*W,)) from the same per-pixel rays."""
+    device = next(model.parameters()).device
+    rays, _ = ops.get_rays_image(H, W, fx, fy, cx, cy, c2w, scene_box.aabb, device, center_pixels=center_pixels,
+                                 near_far_override=(None, None), apply_clamp=True)
+    normal, rgb, depth, acc = render_normals(model, rays, ray_samples, params=params, active_module=active_module,
+                                             bg_color_default=bg_color_default, min_weight=min_weight,
+                                             chunk_rays=chunk_rays, normalize=normalize)
+    return normal.view(H, W, 3), rgb.view(H, W, 3).float().clamp_(0, 1), depth.view(-1), acc.view(-1)
+
+
+@torch.no_grad()
 def render_image(model, *, H: int, W: int, fx: float, fy: float, cx: float, cy: float, c2w: Tensor, scene_box,
                  params=None, active_module: Optional[int] = None, ray_samples: int = 64, chunk_points: int = 1 << 16,
                  bg_color_default: str = "white", center_pixels: bool = True, use_amp: bool = False,

@@ -559,6 +559,28 @@ int acn_mlp_train_bwd_input(const float* h0, const float* sh, const float* out, 
                             const acn_mlp* w, float* gh0, float* gsh, void* workspace, void* stream);
 int acn_mlp_train_bwd_input_img(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
                                 const float* img, float* gh0, float* gsh, void* stream);
+/* Density and its world-space gradient in one launch (MetaNGP.density and its autograd in the points, evaluation
+ * only): for p = x[m*ld .. +3] (ld >= 3 floats per row), u = (p - aabb_min) / aabb_extent, x01 = clamp(u, lo, hi)
+ * (lo = enc_eps, hi = 1 - enc_eps in fp32), sigma[m] = trunc_exp(sigma_head(relu trunk(hash(x01)))) and
+ * grad[m] = d sigma / d p = (pass / aabb_extent) * sum_l (level l's point derivative . dL/dh0_l), pass = 1 where
+ * lo <= u <= hi (torch's clamp backward).  d sigma / d s = sigma (TruncExp's rule, also where s was clamped).  One
+ * wave per 32-sample tile gathers the 32 hash features into the MFMA operand, runs the sigma branch forward and
+ * backward in registers and contracts dL/dh0 with a second gather of the corner rows; the level terms are added in
+ * acn_hashgrid_bwd_input's tree order, so (sigma, grad) equal, bit for bit, the chain acn_hashgrid_fwd ->
+ * acn_mlp_train_fwd -> acn_mlp_train_bwd_input (gout = e_sigma) -> acn_hashgrid_bwd_input -> * pass / extent.  No
+ * atomics, no partial sums: a row depends on its own sample only.  gate (M) or NULL: a sample with gate[m] <=
+ * gate_min writes sigma = 0 and grad = 0, a tile of 32 gated samples is skipped before any gather, and the other
+ * samples' bits do not depend on the gate.  A NaN coordinate gives NaN outputs for its own row only.
+ * fp32 table, F = 2, L = 16, Linear or Smoothstep, table <= 2 GiB (log2T <= 24): anything else returns
+ * ACN_ERR_UNSUPPORTED before any HIP call.  M == 0 is a no-op.  workspace: acn_mlp_workspace_bytes() device bytes. */
+int acn_field_sigma_grad(const float* x, int64_t M, int64_t ld, const float* table, const int32_t* res, int L,
+                         int log2T, int F, int interp, const float* aabb_min, const float* aabb_extent, float lo,
+                         float hi, const acn_mlp* w, const float* gate, float gate_min, float* sigma, float* grad,
+                         void* workspace, void* stream);
+/* Normal map compositing: normal[n] = sum_s weights[n,s] * (-g / max(|g|, 1e-9)), g = grad[n*S + s] (N*S, 3); the
+ * terms in fp32, accumulated in float64 in sample order and rounded once (deterministic); g = 0 adds exactly 0.
+ * N == 0 is a no-op. */
+int acn_normal_composite(const float* grad, const float* weights, int64_t N, int S, float* normal, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Episodic task routing (data.hip).  Replaces TaskDataset's region clip + micro-cell assignment
@@ -804,6 +826,12 @@ int acn_mlp_train_bwd_input_exact(const float* h0, const float* sh, const float*
                             const acn_mlp* w, float* gh0, float* gsh, void* workspace, void* stream);
 int acn_mlp_train_bwd_input_img_exact(const float* h0, const float* sh, const float* out, const float* gout, int64_t M,
                                 const float* img, float* gh0, float* gsh, void* stream);
+/* acn_field_sigma_grad with exact-fp32 layer products (workspace: acn_mlp_workspace_bytes_exact()); there is no
+ * _amp form */
+int acn_field_sigma_grad_exact(const float* x, int64_t M, int64_t ld, const float* table, const int32_t* res, int L,
+                               int log2T, int F, int interp, const float* aabb_min, const float* aabb_extent, float lo,
+                               float hi, const acn_mlp* w, const float* gate, float gate_min, float* sigma,
+                               float* grad, void* workspace, void* stream);
 size_t acn_mlp_pairs_workspace_bytes_exact(int K);
 int acn_mlp_pack_pairs_exact(const acn_mlp* const* w, int K, void* workspace, void* stream);
 int acn_mlp_train_fwd_pairs_exact(const float* h0, const float* sh, const int64_t* seg, int K, const void* workspace,

@@ -11,7 +11,7 @@ MLP backward, the hash grid's and the MLP's input gradients.  --all lists every 
 import argparse, re, sys
 
 HOT = ("render_ws_kernel", "render_slots_kernel", "render_wss_kernel", "ep_field_kernel", "mlp_bwd_dw_pc_kernel",
-       "mlp_bwd_dw_pairs_pc_kernel", "hashgrid_bwd_input", "mlp_bwd_input")
+       "mlp_bwd_dw_pairs_pc_kernel", "hashgrid_bwd_input", "mlp_bwd_input", "field_sigma_grad")
 FIELDS = {"VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "VGPRs Spill": "vspill",
           "SGPRs Spill": "sspill", "Occupancy [waves/SIMD]": "occ"}
 
