@@ -169,6 +169,8 @@ SIGNATURES = {
     "acn_field_sigma_grad": ([vp, i64, i64, vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, vp, vp, f32, vp, vp, vp, vp],
                              C.c_int),
     "acn_normal_composite": ([vp, vp, i64, i32, vp, vp], C.c_int),
+    "acn_distortion_packed": ([vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp], C.c_int),
+    "acn_distortion_dense": ([vp, vp, i64, i32, vp, vp, vp, vp], C.c_int),
     # routed.hip
     "acn_routed_workspace_bytes": ([i64, i32], C.c_size_t),
     "acn_routed_count": ([vp, i64, i32, vp, vp, i32, vp, vp, vp, sz, vp], C.c_int),

@@ -43,6 +43,24 @@ __device__ __forceinline__ double lane_f64(double v, int l) {
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
+// Inclusive scan and sum of one double per lane over the wave (the segmented per-ray scans of occ.hip and the
+// distortion loss of loss.hip: one wave per ray, 64 samples per step).  Fixed order: deterministic; every lane of
+// wave_sum_d ends with the same bits (each xor step adds the same two values on both sides).
+__device__ __forceinline__ double wave_incl_scan(double v, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double y = __shfl_up(v, off);
+        if (lane >= off) v += y;
+    }
+    return v;
+}
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
 // compute_mse_loss in color_space "linear" (nerfs/losses.py:10-32, color_space.py:13-19, 22-66): pred.clamp(0,1)
 // against gt.clamp(0,1) -> srgb_to_linear -> clamp(0,1); float scalars and powf as the torch ops (loss.hip and
 // the fused training compositing in render.hip)

@@ -8,7 +8,8 @@
 // Float semantics follow the torch ops: scalars as float (12.92f, 0.055f, 1.055f, 0.04045f), powf with
 // the float exponent, clamps that pass NaN through, and mse_loss_backward's double `2 / numel` factor.
 // Also here, as the other small per-ray reduction: acn_normal_composite, the weighted sum of the samples' unit
-// normals of a rendered normal map.
+// normals of a rendered normal map, and the distortion regulariser of the weights along a ray with its
+// gradient (acn_distortion_packed / acn_distortion_dense).
 #include "acn_device.h"
 #include "acn_internal.h"
 
@@ -147,7 +148,135 @@ __global__ void __launch_bounds__(256) normal_composite_kernel(const float* __re
     normal[3 * n + 2] = (float)az;
 }
 
+// Distortion loss (acn_distortion_packed / acn_distortion_dense): for one ray with weights w_i over the
+// intervals [s_i, s_i + d_i], midpoints m_i = s_i + d_i / 2 non-decreasing along the ray,
+//   L        = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i = sum_i [ 2 w_i (m_i W_<i - WM_<i) + w_i^2 d_i / 3 ]
+//   dL/dw_i  = 2 [ (m_i W_<i - WM_<i) + (WM_>i - m_i W_>i) ] + 2/3 w_i d_i
+// with W, WM the prefix sums of w and w m.  One wave per ray, 64 samples per step (the shape of
+// packed_weights_bwd_kernel): pass 1 sums w and w m over the ray, pass 2 walks front to back with two scans.  m W - WM
+// is a difference of nearly equal numbers when t is large against the sample spacing, so the sums, carries and terms
+// are double and each output is rounded to fp32 once.  No atomics, no LDS: bitwise reproducible.
+// DENSE: w, t (N, S), the compositing's own intervals (s_i = t_i, d_i = max(t_{i+1} - t_i, 1e-4), the last d copied
+// from its predecessor: volume_render's dists).  Packed: [t0_i, t1_i] of samples starts[r] .. + counts[r], cut at M.
+struct DistortionArgs {
+    const float *w, *t0, *t1;        // dense: t0 = t_vals, t1 unused
+    const int64_t *starts, *counts;  // packed only
+    int64_t M, N;
+    int32_t S;                       // dense only
+    const float* ray_scale;          // (N) or NULL
+    float *loss, *grad_w;            // grad_w may be NULL
+};
+
+// midpoint and width of sample k (< n) of the ray whose first sample is b
+template <bool DENSE>
+__device__ __forceinline__ void distortion_interval(const DistortionArgs& a, int64_t b, int64_t k, int64_t n, double& m,
+                                                    double& d) {
+    if (DENSE) {
+        const int64_t j = k + 1 < n ? k : n - 2;   // the last sample takes its predecessor's width (n >= 2)
+        const float df = acn::clamp_min_nan(a.t0[b + j + 1] - a.t0[b + j], 1e-4f);
+        d = (double)df;
+        m = (double)a.t0[b + k] + 0.5 * d;
+    } else {
+        const double s = (double)a.t0[b + k], e = (double)a.t1[b + k];
+        d = e - s;
+        m = 0.5 * (s + e);
+    }
+}
+
+template <bool DENSE>
+__global__ void __launch_bounds__(256) distortion_kernel(DistortionArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < a.N; r += nw) {
+        int64_t b, n;
+        if (DENSE) {
+            b = r * a.S;
+            n = a.S;
+        } else {
+            b = a.starts[r];
+            n = a.counts[r];
+            if (b < 0 || b > a.M || n < 0) n = 0;   // a range outside the samples is empty, one past M is cut
+            if (n > a.M - b) n = a.M - b;
+        }
+        const double scale = a.ray_scale ? (double)a.ray_scale[r] : 1.0;
+        if (scale == 0.0) {   // wave-uniform: zeros, and the ray's t values (NaN for an invalid ray) are not read
+            if (a.grad_w)
+                for (int64_t k = lane; k < n; k += 64) a.grad_w[b + k] = 0.0f;
+            if (lane == 0) a.loss[r] = 0.0f;
+            continue;
+        }
+        double wt = 0.0, wmt = 0.0;   // sum of w and of w m over the ray
+        for (int64_t s0 = 0; s0 < n; s0 += 64) {
+            const int64_t k = s0 + lane;
+            double w = 0.0, wm = 0.0;
+            if (k < n) {
+                double m, d;
+                distortion_interval<DENSE>(a, b, k, n, m, d);
+                w = (double)a.w[b + k];
+                wm = w * m;
+            }
+            wt += acn::wave_sum_d(w);
+            wmt += acn::wave_sum_d(wm);
+        }
+        double cw = 0.0, cwm = 0.0;   // sums over the samples before this step
+        double acc = 0.0;             // this lane's share of the loss
+        for (int64_t s0 = 0; s0 < n; s0 += 64) {
+            const int64_t k = s0 + lane;
+            const bool v = k < n;
+            double w = 0.0, m = 0.0, d = 0.0;
+            if (v) {
+                distortion_interval<DENSE>(a, b, k, n, m, d);
+                w = (double)a.w[b + k];
+            }
+            const double wm = w * m;
+            const double iw = acn::wave_incl_scan(w, lane), iwm = acn::wave_incl_scan(wm, lane);
+            if (v) {
+                const double w_le = cw + iw, wm_le = cwm + iwm;   // W_<=i, WM_<=i
+                const double before = m * (w_le - w) - (wm_le - wm);       // sum_{j<i} w_j (m_i - m_j)
+                acc += 2.0 * w * before + w * w * d * (1.0 / 3.0);
+                if (a.grad_w) {
+                    const double after = (wmt - wm_le) - m * (wt - w_le);  // sum_{j>i} w_j (m_j - m_i)
+                    a.grad_w[b + k] = (float)(scale * (2.0 * (before + after) + (2.0 / 3.0) * w * d));
+                }
+            }
+            cw += __shfl(iw, 63);
+            cwm += __shfl(iwm, 63);
+        }
+        acc = acn::wave_sum_d(acc);
+        if (lane == 0) a.loss[r] = (float)(scale * acc);
+    }
+}
+
+template <bool DENSE>
+int launch_distortion(const DistortionArgs& a, void* stream, const char* what) {
+    const int64_t wgs = (a.N + 3) / 4;   // 4 waves (rays) per 256-thread workgroup, grid-stride past 4096 of them
+    hipLaunchKernelGGL(distortion_kernel<DENSE>, dim3((unsigned)(wgs < 4096 ? wgs : 4096)), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    return acn_check_launch(what);
+}
+
 }  // namespace
+
+extern "C" int acn_distortion_packed(const float* weights, const float* t_starts, const float* t_ends, int64_t M,
+                                     const int64_t* chunk_starts, const int64_t* chunk_cnts, int64_t N,
+                                     const float* ray_scale, float* loss, float* grad_w, void* stream) {
+    ACN_REQUIRE(N >= 0 && M >= 0, "acn_distortion_packed: N and M must be >= 0 (got %lld, %lld)", (long long)N,
+                (long long)M);
+    if (N == 0) return ACN_OK;
+    ACN_REQUIRE(chunk_starts && chunk_cnts && loss, "acn_distortion_packed: NULL pointer");
+    ACN_REQUIRE(M == 0 || (weights && t_starts && t_ends), "acn_distortion_packed: NULL sample array");
+    DistortionArgs a{weights, t_starts, t_ends, chunk_starts, chunk_cnts, M, N, 0, ray_scale, loss, grad_w};
+    return launch_distortion<false>(a, stream, "acn_distortion_packed");
+}
+
+extern "C" int acn_distortion_dense(const float* weights, const float* t_vals, int64_t N, int S,
+                                    const float* ray_scale, float* loss, float* grad_w, void* stream) {
+    ACN_REQUIRE(N >= 0 && S >= 2, "acn_distortion_dense: N must be >= 0 and S >= 2 (got %lld, %d)", (long long)N, S);
+    if (N == 0) return ACN_OK;
+    ACN_REQUIRE(weights && t_vals && loss, "acn_distortion_dense: NULL pointer");
+    DistortionArgs a{weights, t_vals, nullptr, nullptr, nullptr, N * (int64_t)S, N, S, ray_scale, loss, grad_w};
+    return launch_distortion<true>(a, stream, "acn_distortion_dense");
+}
 
 extern "C" int acn_mse_linear_fwd(const float* pred, const float* gt, int64_t n, float* loss, void* stream) {
     ACN_REQUIRE(n >= 1 && pred && gt && loss, "acn_mse_linear_fwd: bad arguments");

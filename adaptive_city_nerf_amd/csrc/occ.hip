@@ -15,6 +15,7 @@
 //     step), deterministic (no atomics), with fused backward.
 // Float op order of the traversal follows oracle/occ_oracle.c exactly (-ffp-contract=off), so the
 // sample lists agree bit for bit with the oracle.
+#include "acn_device.h"
 #include "acn_internal.h"
 
 using namespace acn;
@@ -349,22 +350,7 @@ __global__ void __launch_bounds__(256) occ_union_kernel(UnionArgs a) {
 // ------------------------------------------------------------------------------------------
 // nerfacc render_weight_from_density over packed samples (one wave per ray, 64 samples per step):
 // sdt = sigma * (t1 - t0); alpha = 1 - exp(-sdt); trans = exp(-exclusive_sum(sdt)); w = trans * alpha.
-// The segmented exclusive sum is carried in double.
-__device__ __forceinline__ double wave_incl_scan(double v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double y = __shfl_up(v, off);
-        if (lane >= off) v += y;
-    }
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
+// The segmented exclusive sum is carried in double (wave_incl_scan / wave_sum_d: acn_device.h).
 struct PackedWArgs {
     const float *sigmas, *t0, *t1;
     const int64_t *starts, *counts;

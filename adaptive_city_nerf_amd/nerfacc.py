@@ -16,6 +16,8 @@ read unchanged:
   ``render_weight_from_density``, ``render_visibility_from_density``, ``accumulate_along_rays``:
   packed (ray-major) sample arrays; weights and accumulation are HIP segmented scans / sums with
   HIP backward kernels behind autograd Functions.
+* ``distortion`` (``nerfacc.losses.distortion``): the mip-NeRF 360 regulariser of the weights along each ray,
+  loss and gradient from one HIP launch.
 
 Parity with nerfacc itself is UNPINNED (no nerfacc code or fixture exists in this environment); the
 kernels are checked bit for bit (traversal) / within tolerance (compositing) against the oracle's
@@ -30,12 +32,12 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from . import occ_ops
+from . import occ_ops, ops
 from ._lib import AcnError
 
 __all__ = ["OccGridEstimator", "ray_aabb_intersect", "traverse_grids", "pack_info",
            "render_transmittance_from_density", "render_weight_from_density", "render_visibility_from_density",
-           "accumulate_along_rays"]
+           "accumulate_along_rays", "distortion"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -141,6 +143,122 @@ def accumulate_along_rays(weights: Tensor, values: Optional[Tensor] = None, ray_
     v = None if values is None else values.reshape(weights.shape[0], -1)
     out = _PackedAccumulateFn.apply(weights, v, ray_indices.long(), pi[:, 0].contiguous(), pi[:, 1].contiguous())
     return out.to(weights.dtype)
+
+
+# ----------------------------------------------------------------------------------------------
+# Distortion loss (nerfacc.losses.distortion, the mip-NeRF 360 regulariser): per ray
+#   L = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i = sum_i [2 w_i (m_i W_<i - WM_<i) + w_i^2 d_i / 3]
+# over the intervals' midpoints m (non-decreasing along a ray) and widths d; the t values carry no gradient.
+class _DistortionFn(torch.autograd.Function):
+    """One HIP launch (acn_distortion_packed / acn_distortion_dense) that returns the per-ray loss and keeps
+    d loss / d weights for the backward, which is g_loss[ray] * grad_w.  ``starts`` None: the dense layout
+    (``ta`` = t_vals (N, S), the compositing's own intervals); else packed samples [ta_i, tb_i] whose rays are
+    ``ray_indices`` (M,), or equal rows of M / N samples when that is None."""
+
+    @staticmethod
+    def forward(ctx, weights, ta, tb, starts, counts, ray_indices, ray_scale, want_grad):
+        if starts is None:
+            loss, grad = ops.distortion_dense(weights, ta, ray_scale, want_grad=want_grad)
+        else:
+            loss, grad = occ_ops.distortion_packed(weights.reshape(-1), ta.reshape(-1), tb.reshape(-1), starts, counts,
+                                                   ray_scale, want_grad=want_grad)
+        ctx.set_materialize_grads(False)
+        ctx.shape = weights.shape
+        ctx.by_index = ray_indices is not None
+        if want_grad:
+            ctx.save_for_backward(grad, *((ray_indices,) if ctx.by_index else ()))
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        if g_loss is None or not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        grad = ctx.saved_tensors[0]
+        if ctx.by_index:
+            g = g_loss.index_select(0, ctx.saved_tensors[1]) * grad
+        else:
+            g = (g_loss.unsqueeze(1) * grad.view(g_loss.shape[0], -1))
+        return (g.view(ctx.shape),) + (None,) * 7
+
+
+def _dense_intervals(t_vals: Tensor) -> Tuple[Tensor, Tensor]:
+    """float64 (midpoints, widths) of the compositing's own intervals of (N, S) t values: s_i = t_i,
+    d_i = max(t_{i+1} - t_i, 1e-4) in t's precision with the last d copied from its predecessor (volume_render's
+    ``dists``)."""
+    t = t_vals.detach()
+    d = (t[:, 1:] - t[:, :-1]).clamp_min(1e-4)
+    d = torch.cat([d, d[:, -1:]], dim=1).double()
+    return t.double() + 0.5 * d, d
+
+
+def _distortion_torch(weights: Tensor, m: Tensor, d: Tensor, ray_indices: Optional[Tensor] = None,
+                      n_rays: Optional[int] = None, ray_scale: Optional[Tensor] = None) -> Tensor:
+    """The kernels' O(S) formula as torch ops with float64 scans (CPU tensors, other dtypes than fp32, and inside
+    second_order(): differentiable any number of times in the weights).  ``m`` / ``d``: float64 midpoints and widths,
+    (N, S) with ``ray_indices`` None, else packed (M,) samples of ``n_rays`` rays.  A ray whose scale is 0 gets an
+    exact 0 whatever its t values are."""
+    w = weights.double()
+    if ray_scale is not None:
+        live = ray_scale.detach() != 0
+        keep = live.unsqueeze(1) if ray_indices is None else live.index_select(0, ray_indices)
+        m, d = torch.where(keep, m, torch.zeros_like(m)), torch.where(keep, d, torch.zeros_like(d))
+    if ray_indices is not None:
+        # the rays as rows of a zero-padded (n_rays, longest ray) array (a host read of that length: this is not the
+        # hot path); a padded sample has weight 0 and adds exactly nothing
+        cnt = torch.bincount(ray_indices, minlength=n_rays)[:n_rays]
+        col = torch.arange(w.shape[0], device=w.device) - (torch.cumsum(cnt, 0) - cnt).index_select(0, ray_indices)
+        rows = w.new_zeros(3, n_rays, int(cnt.max().item()) if cnt.numel() else 0)
+        w, m, d = rows.index_put((torch.arange(3, device=w.device)[:, None], ray_indices[None], col[None]),
+                                 torch.stack([w, m, d]))
+    wm = w * m
+    w_lt, wm_lt = torch.cumsum(w, 1) - w, torch.cumsum(wm, 1) - wm
+    loss = (2.0 * w * (m * w_lt - wm_lt) + w * w * d / 3.0).sum(1)
+    if ray_scale is not None:
+        loss = torch.where(live, loss * ray_scale.double(), torch.zeros_like(loss))
+    return loss.to(weights.dtype)
+
+
+def _distortion_fused(weights: Tensor) -> bool:
+    from .ray_rendering import _second_order
+    return weights.is_cuda and weights.dtype == torch.float32 and not _second_order()
+
+
+def distortion(weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Optional[Tensor] = None,
+               n_rays: Optional[int] = None) -> Tensor:
+    """(n_rays,) distortion loss of each ray's weights (nerfacc.losses.distortion; Barron et al., mip-NeRF 360):
+    sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 (t_ends_i - t_starts_i), m the intervals' midpoints, which must
+    be non-decreasing along a ray.  Packed (M,) samples with their ``ray_indices`` (ray-sorted, as the marching
+    returns them; without them the samples are one ray), or batched (n_rays, n_samples) tensors.  Differentiable in
+    ``weights`` (one fused HIP launch forward, one multiply backward); the t values carry no gradient."""
+    if not (weights.shape == t_starts.shape == t_ends.shape) or weights.dim() not in (1, 2):
+        raise AcnError(f"distortion: weights, t_starts and t_ends must share one shape, (M,) or (n_rays, n_samples); "
+                       f"got {tuple(weights.shape)}, {tuple(t_starts.shape)}, {tuple(t_ends.shape)}")
+    t0, t1 = t_starts.detach(), t_ends.detach()
+    dev = weights.device
+    if weights.dim() == 2:
+        if ray_indices is not None:
+            raise AcnError("distortion: ray_indices go with packed (M,) samples, not with (n_rays, n_samples)")
+        N, S = weights.shape
+        if n_rays is not None and int(n_rays) != N:
+            raise AcnError(f"distortion: n_rays = {n_rays} but weights has {N} rows")
+        if not _distortion_fused(weights):
+            return _distortion_torch(weights, 0.5 * (t0.double() + t1.double()), t1.double() - t0.double())
+        starts = torch.arange(N, dtype=torch.long, device=dev) * S
+        return _DistortionFn.apply(weights, t0, t1, starts, torch.full_like(starts, S), None, None,
+                                   torch.is_grad_enabled() and weights.requires_grad)
+    if ray_indices is not None and ray_indices.shape != weights.shape:
+        raise AcnError(f"distortion: ray_indices must be ({weights.shape[0]},), got {tuple(ray_indices.shape)}")
+    if not _distortion_fused(weights):
+        ri = torch.zeros(weights.shape[0], dtype=torch.long, device=dev) if ray_indices is None else ray_indices.long()
+        if n_rays is None:
+            n_rays = 1 if ray_indices is None else (int(ri.max().item()) + 1 if ri.numel() else 0)
+        return _distortion_torch(weights, 0.5 * (t0.double() + t1.double()), t1.double() - t0.double(), ri,
+                                 int(n_rays))
+    starts, counts = _packed(None, ray_indices, n_rays, weights.numel(), dev)
+    ri = ray_indices.long() if ray_indices is not None else None
+    return _DistortionFn.apply(weights, t0, t1, starts, counts, ri, None,
+                               torch.is_grad_enabled() and weights.requires_grad)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import AcnError, check, ptr, require_hip, stream_of
-from .ops import _experts_array, _f32, pack_experts
+from .ops import _experts_array, _f32, _ray_scale_arg, pack_experts
 
 I64 = torch.int64
 # single-pass traversal: per-ray scratch rows of SINGLE_PASS_CAP samples while the scratch stays under
@@ -219,6 +219,36 @@ def packed_accumulate_bwd(w, values, ray_indices, g_out, need_w: bool, need_v: b
     check(_lib.lib().acn_packed_accumulate_bwd(ptr(ww), ptr(v), Cc, ptr(_as_i64(ray_indices)), M, ptr(g), ptr(gw),
                                                ptr(gv), stream_of(ww)), "acn_packed_accumulate_bwd")
     return gw, gv
+
+
+def distortion_packed(weights, t0, t1, starts, counts, ray_scale: Optional[torch.Tensor] = None,
+                      want_grad: bool = True):
+    """(loss (N,), d loss / d weights (M,) or None) of the mip-NeRF 360 distortion loss over packed samples
+    (acn_distortion_packed): intervals [t0_i, t1_i], midpoints non-decreasing along a ray,
+    loss = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 (t1_i - t0_i), times ``ray_scale`` (N,) when given.  One
+    launch; prefix sums in float64, one fp32 rounding per output; bitwise reproducible.  An empty ray gets 0; a ray
+    whose scale is exactly 0 gets zeros and its t values are not read.  The rays' ranges partition the samples, as
+    pack_info's do (a sample no ray covers is not written, as in packed_weights); a range reaching past M is cut
+    at M by the kernel."""
+    if weights.dim() != 1 or t0.shape != weights.shape or t1.shape != weights.shape:
+        raise AcnError(f"distortion_packed: weights, t0 and t1 must be (M,), got {tuple(weights.shape)}, "
+                       f"{tuple(t0.shape)}, {tuple(t1.shape)}")
+    if starts.dim() != 1 or counts.shape != starts.shape:
+        raise AcnError(f"distortion_packed: starts and counts must be (N,), got {tuple(starts.shape)}, "
+                       f"{tuple(counts.shape)}")
+    require_hip(weights, "distortion_packed")
+    ww, a, b = _f32(weights), _f32(t0), _f32(t1)
+    st, ct = _as_i64(starts), _as_i64(counts)
+    dev = ww.device
+    if any(t.device != dev for t in (a, b, st, ct)):
+        raise AcnError("distortion_packed: every tensor must be on the weights' device")
+    M, N = ww.numel(), st.numel()
+    rs = _ray_scale_arg(ray_scale, N, dev, "distortion_packed")
+    loss = torch.empty(N, device=dev, dtype=torch.float32)
+    grad = torch.empty(M, device=dev, dtype=torch.float32) if want_grad else None
+    check(_lib.lib().acn_distortion_packed(ptr(ww), ptr(a), ptr(b), M, ptr(st), ptr(ct), N, ptr(rs), ptr(loss),
+                                           ptr(grad), stream_of(ww)), "acn_distortion_packed")
+    return loss, grad
 
 
 def cell_points(cell_indices: torch.Tensor, u: Optional[torch.Tensor], aabb: Sequence[float], res) -> torch.Tensor:

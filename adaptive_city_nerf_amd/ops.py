@@ -870,6 +870,40 @@ def normal_composite(grad: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _ray_scale_arg(ray_scale: Optional[torch.Tensor], N: int, device, what: str) -> Optional[torch.Tensor]:
+    if ray_scale is None:
+        return None
+    rs = _f32(ray_scale).reshape(-1)
+    if rs.numel() != N or rs.device != device:
+        raise AcnError(f"{what}: ray_scale must be ({N},) on the weights' device, got {tuple(ray_scale.shape)} on "
+                       f"{ray_scale.device}")
+    return rs
+
+
+def distortion_dense(weights: torch.Tensor, t_vals: torch.Tensor, ray_scale: Optional[torch.Tensor] = None,
+                     want_grad: bool = True):
+    """(loss (N,), d loss / d weights (N, S) or None) of the mip-NeRF 360 distortion loss over the compositing's own
+    intervals (acn_distortion_dense): s_i = t_i, d_i = max(t_{i+1} - t_i, 1e-4) with the last d copied from its
+    predecessor (volume_render's ``dists``), m_i = s_i + d_i / 2,
+    loss = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i, times ``ray_scale`` (N,) when given.  One launch; prefix
+    sums in float64, one fp32 rounding per output; bitwise reproducible.  A ray whose scale is exactly 0 gets zeros and
+    its t values are not read."""
+    if weights.dim() != 2 or weights.shape[1] < 2 or t_vals.shape != weights.shape:
+        raise AcnError(f"distortion_dense: weights and t_vals must both be (N, S >= 2), got {tuple(weights.shape)} and "
+                       f"{tuple(t_vals.shape)}")
+    require_hip(weights, "distortion_dense")
+    wv, tv = _f32(weights), _f32(t_vals)
+    if tv.device != wv.device:
+        raise AcnError("distortion_dense: t_vals must be on the weights' device")
+    N, S = wv.shape
+    rs = _ray_scale_arg(ray_scale, N, wv.device, "distortion_dense")
+    loss = torch.empty(N, device=wv.device, dtype=torch.float32)
+    grad = torch.empty(N, S, device=wv.device, dtype=torch.float32) if want_grad else None
+    check(_lib.lib().acn_distortion_dense(ptr(wv), ptr(tv), N, int(S), ptr(rs), ptr(loss), ptr(grad), stream_of(wv)),
+          "acn_distortion_dense")
+    return loss, grad
+
+
 def sample_stratified(rays: torch.Tensor, S: int, jitter: Optional[torch.Tensor], aabb_min, aabb_extent,
                       eps: float):
     """Training-path sampler (acn_sample_stratified): t_vals (N,S), x01 (N*S,3) in the expert's unit box

@@ -289,7 +289,8 @@ def _routed_train_ok(model, rays, active_module) -> bool:
             and rays.dtype == torch.float32 and all(s._fusable for s in model.submodules) and not _second_order())
 
 
-def _render_routed(model, rays: Tensor, S: int, params, u: Optional[Tensor], bg_color_default: str, sigma_scale):
+def _render_routed(model, rays: Tensor, S: int, params, u: Optional[Tensor], bg_color_default: str, sigma_scale,
+                   return_t_vals: bool = False):
     """Differentiable render of the routed container (training / runtime_adapt, ray_rendering.py:290-345
     over MetaContainer.forward :275-343): routing + per-expert pair lists on the GPU (routed.hip, one
     host sync for the segment sizes), per expert the HIP hash grid (autograd to its table) and the fused
@@ -315,7 +316,8 @@ def _render_routed(model, rays: Tensor, S: int, params, u: Optional[Tensor], bg_
     y = torch.cat(outs, 0) if len(outs) > 1 else (outs[0] if outs else rays.new_zeros(0, 4))
     rgb_sigma = _BlendFn.apply(y, pw, pmap, pidx).view(N, S, 4)
     bg_rgb = _get_bg_rgb(model, rays[:, 3:6], params, rgb_sigma, N=N, bg_color_default=bg_color_default)
-    return volume_render(rgb_sigma, t_vals, bg_rgb=bg_rgb, raw_rgb=False, raw_sigma=False, sigma_scale=sigma_scale)
+    out = volume_render(rgb_sigma, t_vals, bg_rgb=bg_rgb, raw_rgb=False, raw_sigma=False, sigma_scale=sigma_scale)
+    return out + (t_vals,) if return_t_vals else out
 
 
 def _fused_experts(model, params, active_module, render_table: bool = False):
@@ -363,8 +365,12 @@ def _fused_background(model, bg_color_default: str, N: int, device):
 
 
 def render_rays_stratified(model, rays: Tensor, ray_samples: int, params=None, active_module: Optional[int] = None,
-                           bg_color_default: str = "white", chunk: int = 1_000_000, sigma_scale=1.0, **kwargs):
+                           bg_color_default: str = "white", chunk: int = 1_000_000, sigma_scale=1.0,
+                           return_t_vals: bool = False, **kwargs):
     """Stratified renderer: rgb (N,3), depth (N,), weights (N,S), acc (N,) (:290-345).
+
+    ``return_t_vals`` (an extension) appends the (N,S) sample depths the weights belong to, in the caller's ray
+    order, as a fifth value: what ``distortion_loss`` needs next to the weights.
 
     Rays that require grad take the composed path (no fused render, sampler or routed pair kernels): the
     gradient reaches the origins and directions, ``rays[:, :6]``, through the sample points, the field's
@@ -389,8 +395,11 @@ def render_rays_stratified(model, rays: Tensor, ray_samples: int, params=None, a
                                                        0 if len(specs) == 1 else None, bg,
                                                        sigma_scale=float(sigma_scale), tau=tau, jitter=jitter,
                                                        packed=packed, want_weights=want_weights)
-            return (rgb.to(rays.dtype), depth.to(rays.dtype), None if w is None else w.to(rays.dtype),
-                    acc.to(rays.dtype))
+            out = (rgb.to(rays.dtype), depth.to(rays.dtype), None if w is None else w.to(rays.dtype),
+                   acc.to(rays.dtype))
+            if return_t_vals:   # the kernel keeps its t values in registers: the same jitter through the torch form
+                out += (stratified_t_vals(rays[:, 6], rays[:, 7], ray_samples, randomized=model.training, u=jitter),)
+            return out
     sub = _train_expert(model, active_module) if FUSED_TRAIN_SAMPLER and not diff_rays else None
     if sub is not None and rays.is_cuda and rays.dtype == torch.float32 and sub._fused_train_ok(rays):
         # differentiable single-expert path (training, inner loops): one sampler launch (t-values,
@@ -429,12 +438,14 @@ def render_rays_stratified(model, rays: Tensor, ray_samples: int, params=None, a
             bg_rgb = bg_rgb.index_select(0, order)   # (last_sample reads the visiting-order samples already)
         out = volume_render(rgb_sigma, t_vals, bg_rgb=bg_rgb, raw_rgb=False, raw_sigma=False,
                             sigma_scale=sigma_scale)
+        if return_t_vals:
+            out += (t_vals,)
         if order is None:
             return out
         return tuple(None if x is None else x.index_select(0, inv) for x in out)   # the caller's order
     if not diff_rays and _routed_train_ok(model, rays, active_module):
         return _render_routed(model, rays, ray_samples, params, kwargs.get("jitter_u"), bg_color_default,
-                              sigma_scale)
+                              sigma_scale, return_t_vals)
     # composed (differentiable) path -- same structure as the reference
     o, d = rays[:, :3], rays[:, 3:6]
     near, far = rays[:, 6], rays[:, 7]
@@ -446,7 +457,8 @@ def render_rays_stratified(model, rays: Tensor, ray_samples: int, params=None, a
     outs = [model_eff(id6[s: s + chunk], params=params) for s in range(0, id6.shape[0], chunk)]
     rgb_sigma = torch.cat(outs, dim=0).view(pts.shape[0], pts.shape[1], 4)
     bg_rgb = _get_bg_rgb(model, dirs[:, 0], params, rgb_sigma, N=rgb_sigma.size(0), bg_color_default=bg_color_default)
-    return volume_render(rgb_sigma, t_vals, bg_rgb=bg_rgb, raw_rgb=False, raw_sigma=False, sigma_scale=sigma_scale)
+    out = volume_render(rgb_sigma, t_vals, bg_rgb=bg_rgb, raw_rgb=False, raw_sigma=False, sigma_scale=sigma_scale)
+    return out + (t_vals,) if return_t_vals else out
 
 
 # ============================== Occupancy rendering (Soft MoE) ===============================
@@ -653,6 +665,10 @@ def render_rays(model, rays, *args, **kwargs):
         if getattr(model, "warned_occ_ready", False) is False:
             warnings.warn("[OCC] Using nerfacc occupancy renderer (warmup concluded).")
             model.warned_occ_ready = True
+        if kwargs.get("return_t_vals"):
+            raise ops.AcnError("render_rays(return_t_vals=True): the occupancy renderer has no (N,S) t values; take "
+                               "the distortion of its packed samples with nerfacc.distortion")
+        kwargs.pop("return_t_vals", None)
         kwargs.pop("ray_samples", None)
         kwargs.pop("_want_weights", None)
         kwargs.pop("sigma_scale", None)
@@ -702,6 +718,35 @@ def render_normals(model, rays: Tensor, ray_samples: int, params=None, active_mo
     else:
         rgb, depth, acc = (torch.cat([o[i] for o in outs], 0) if outs else rays.new_zeros(0) for i in range(3))
     return normal, rgb, depth, acc
+
+
+def distortion_loss(weights: Tensor, t_vals: Tensor, rays: Optional[Tensor] = None, reduction: str = "mean") -> Tensor:
+    """The mip-NeRF 360 distortion regulariser of a stratified render: per ray
+    sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i over the compositing's own intervals (s_i = t_i,
+    d_i = volume_render's ``dists``, m_i = s_i + d_i / 2), for the (N,S) ``weights`` and ``t_vals`` of
+    ``render_rays_stratified(..., return_t_vals=True)``.  ``rays`` (N, >=8) normalises every ray to unit length
+    (the loss times 1 / (far - near); a ray without far > near, e.g. an invalid one with NaN bounds, contributes an
+    exact 0).  ``reduction``: none (N,) | mean | sum.  Differentiable in the weights (loss and gradient from one
+    HIP launch, acn_distortion_dense); the t values carry no gradient."""
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError(f"distortion_loss: reduction must be none, mean or sum, got {reduction!r}")
+    if weights.dim() != 2 or weights.shape[1] < 2 or t_vals.shape != weights.shape:
+        raise ops.AcnError(f"distortion_loss: weights and t_vals must both be (N, S >= 2), got {tuple(weights.shape)} "
+                           f"and {tuple(t_vals.shape)}")
+    scale = None
+    if rays is not None:
+        if rays.dim() != 2 or rays.shape[0] != weights.shape[0] or rays.shape[1] < 8:
+            raise ops.AcnError(f"distortion_loss: rays must be ({weights.shape[0]}, >=8), got {tuple(rays.shape)}")
+        near, far = rays.detach()[:, 6].to(weights.device), rays.detach()[:, 7].to(weights.device)
+        scale = torch.where(far > near, 1.0 / (far - near), torch.zeros_like(far))
+    if nerfacc._distortion_fused(weights):
+        loss = nerfacc._DistortionFn.apply(weights, t_vals.detach(), None, None, None, None, scale,
+                                           torch.is_grad_enabled() and weights.requires_grad)
+    else:
+        loss = nerfacc._distortion_torch(weights, *nerfacc._dense_intervals(t_vals), ray_scale=scale)
+    if reduction == "none":
+        return loss
+    return loss.mean() if reduction == "mean" else loss.sum()
 
 
 def _normal_composite_torch(grad: Tensor, weights: Tensor) -> Tensor:

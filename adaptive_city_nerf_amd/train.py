@@ -28,7 +28,7 @@ from . import ops
 from ._lib import graph_capture
 from .color_space import color_space_transformer
 from .optim import FusedAdam
-from .ray_rendering import render_rays
+from .ray_rendering import distortion_loss, render_rays
 
 
 class _MSELinearFn(torch.autograd.Function):
@@ -66,9 +66,30 @@ def compute_mse_loss(P, model, data, params=None, active_module=None, reduction:
     return mse_color_loss(pred_rgb, gt_rgb, P.color_space, reduction)
 
 
+def compute_loss(P, model, data, params=None, active_module=None, reduction: str = "mean",
+                 distortion_weight: float = 0.0, **render_kwargs):
+    """compute_mse_loss plus ``distortion_weight`` times the mean distortion loss of the render's weights
+    (ray_rendering.distortion_loss, every ray normalised to unit length): the mip-NeRF 360 regulariser against
+    semi-transparent fog and floaters between the camera and the surface.  With weight 0 it is compute_mse_loss, from
+    the same calls.  The regulariser needs the stratified renderer's (N,S) weights and t values: with the occupancy
+    renderer active, render_rays raises (take nerfacc.distortion of the packed samples instead)."""
+    if not distortion_weight:
+        return compute_mse_loss(P, model, data, params=params, active_module=active_module, reduction=reduction,
+                                **render_kwargs)
+    gt_rgb = data["rgbs"]
+    rays = data["rays"]
+    pred_rgb, _, weights, _, t_vals = render_rays(model, rays, ray_samples=P.ray_samples, params=params,
+                                                  active_module=active_module, chunk=P.chunk_points,
+                                                  return_t_vals=True, **render_kwargs)
+    return mse_color_loss(pred_rgb, gt_rgb, P.color_space, reduction) + \
+        float(distortion_weight) * distortion_loss(weights, t_vals, rays=rays, reduction="mean")
+
+
 def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Optional[float] = 1.0,
-               group=None, shared: Optional[list] = None, grad_scaler=None, **render_kwargs) -> torch.Tensor:
+               group=None, shared: Optional[list] = None, grad_scaler=None, distortion_weight: float = 0.0,
+               **render_kwargs) -> torch.Tensor:
     """One optimizer update of runtime_adapt (runtime_adapt.py:288-313).  Returns the loss (device).
+    ``distortion_weight`` > 0 adds that multiple of the mean distortion loss (compute_loss) to the MSE.
 
     ``group`` (expert parallel): ``rays`` / ``rgbs`` are this rank's shard of the global batch, the
     container's experts are distributed over the group (expert_parallel.adapt_step_expert_parallel);
@@ -76,6 +97,9 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
     With the use_amp MLP precision (ops.set_train_mlp_precision("amp")) the step runs under a GradScaler as
     the reference's does (runtime_adapt.py:237-268): ``grad_scaler`` (a torch.amp.GradScaler; a fresh one when
     None) scales the loss, unscales, skips a non-finite step and updates its scale."""
+    if group is not None and distortion_weight:
+        raise ValueError("adapt_step: the expert-parallel step has no distortion loss (distortion_weight must be 0 "
+                         "with a group)")
     if group is not None and torch.distributed.is_initialized() and torch.distributed.get_world_size(group) > 1:
         from .expert_parallel import HipBackend, adapt_step_expert_parallel
         if active_module is not None:
@@ -87,8 +111,8 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
                                           shared, grad_clip=grad_clip, group=group,
                                           u=render_kwargs.get("jitter_u"))
     optimizer.zero_grad()
-    loss = compute_mse_loss(P, model=base, data={"rays": rays, "rgbs": rgbs}, params=None,
-                            active_module=active_module, reduction="mean", **render_kwargs)
+    loss = compute_loss(P, model=base, data={"rays": rays, "rgbs": rgbs}, params=None, active_module=active_module,
+                        reduction="mean", distortion_weight=distortion_weight, **render_kwargs)
     if ops.TRAIN_MLP_PRECISION == "amp":
         scaler = grad_scaler if grad_scaler is not None else torch.amp.GradScaler("cuda")
         scaler.scale(loss).backward()
@@ -119,10 +143,11 @@ class GraphedAdaptStep:
     are real updates on the first batch).  Only fixed-shape steps are capturable: one expert
     (``active_module``, the C5 / meta-training placement) or a bare MetaNGP -- the routed container's
     per-expert index selection is data-dependent.  Expert-parallel groups are not captured (use
-    adapt_step)."""
+    adapt_step).  ``distortion_weight`` as in adapt_step: the distortion launch and its backward multiply make no
+    host synchronisation, so they are captured with the rest."""
 
     def __init__(self, P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Optional[float] = 1.0,
-                 warmup: int = 2, max_steps: int = 1 << 16, **render_kwargs):
+                 warmup: int = 2, max_steps: int = 1 << 16, distortion_weight: float = 0.0, **render_kwargs):
         from .meta_container import MetaContainer
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedAdaptStep needs FusedAdam")
@@ -134,6 +159,8 @@ class GraphedAdaptStep:
         if render_kwargs.get("jitter_u") is not None:  # caller-supplied jitter: a static input too
             self.static_u = render_kwargs["jitter_u"].detach().clone()
             render_kwargs = dict(render_kwargs, jitter_u=self.static_u)
+        if distortion_weight:
+            render_kwargs = dict(render_kwargs, distortion_weight=float(distortion_weight))
         self.args = (P, base, optimizer, active_module, grad_clip, render_kwargs)
         side = torch.cuda.Stream(rays.device)
         side.wait_stream(torch.cuda.current_stream(rays.device))
@@ -206,7 +233,8 @@ FAST_RUNTIME_ADAPT = os.environ.get("ACN_FAST_ADAPT", "1") != "0"
 
 
 def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional[int] = None,
-                  active_module: Optional[int] = None, grad_clip: Optional[float] = 1.0) -> Dict[str, float]:
+                  active_module: Optional[int] = None, grad_clip: Optional[float] = 1.0,
+                  distortion_weight: float = 0.0) -> Dict[str, float]:
     """runtime_adapt.py:213-315: adapt in place; one pass over the loader (steps=None) or exactly
     ``steps`` updates cycling over it.
 
@@ -214,14 +242,16 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
     runs through one RoutedAdaptStep per (model, optimizer): the first full batch is an eager update, the
     step is then captured and every later batch of that size replays one HIP graph with no host
     synchronisation; a smaller (ragged last) batch runs the same kernels eagerly.  The loss is read once,
-    at the end (the reference reads it every step).  Other configurations take the eager adapt_step."""
+    at the end (the reference reads it every step).  Other configurations take the eager adapt_step, and so does
+    every configuration with ``distortion_weight`` > 0 (adapt_step; the RoutedAdaptStep's fused composite-plus-MSE
+    kernel has no regulariser, so none is built)."""
     device = next(model.parameters()).device
     model.train()
     # the reference clips base.parameters(); parameters outside base get no gradient from the loss
     # (zero_grad sets them to None), so FusedAdam's norm over gradient-carrying tensors is the same
     base = model.submodules[active_module] if active_module is not None else model
     last_loss, step_count = None, 0
-    fast = [None, active_module is None]   # [RoutedAdaptStep, still worth trying]
+    fast = [None, active_module is None and not distortion_weight]   # [RoutedAdaptStep, still worth trying]
     # use_amp: a fresh GradScaler per call (runtime_adapt.py:237); the cached RoutedAdaptStep's scaler restarts too
     amp = ops.TRAIN_MLP_PRECISION == "amp"
     scaler = torch.amp.GradScaler("cuda") if amp else None
@@ -240,7 +270,7 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
             last_loss = fast[0](rays, rgbs)
         else:
             last_loss = adapt_step(P, base, rays, rgbs, optimizer, active_module=active_module, grad_clip=grad_clip,
-                                   grad_scaler=scaler)
+                                   grad_scaler=scaler, distortion_weight=distortion_weight)
         step_count += 1
 
     if steps is None:

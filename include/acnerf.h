@@ -581,6 +581,27 @@ int acn_field_sigma_grad(const float* x, int64_t M, int64_t ld, const float* tab
  * terms in fp32, accumulated in float64 in sample order and rounded once (deterministic); g = 0 adds exactly 0.
  * N == 0 is a no-op. */
 int acn_normal_composite(const float* grad, const float* weights, int64_t N, int S, float* normal, void* stream);
+/* The mip-NeRF 360 distortion loss of the weights along each ray and its gradient in the weights, in one launch
+ * (the regulariser nerfacc ships as nerfacc.losses.distortion; the t values carry no gradient):
+ *   loss[r]  = scale_r * ( sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i )
+ *   grad_w_i = scale_r * ( 2 sum_j w_j |m_i - m_j| + 2/3 w_i d_i )
+ * over ray r's intervals [s_i, s_i + d_i], m_i = s_i + d_i / 2; the midpoints must be non-decreasing along a ray.
+ * Evaluated in O(S) with the exclusive prefix sums of w and w m: one wave per ray, 64 samples per step, the sums and
+ * carries in float64 (m W - WM cancels in fp32 when t is large against the sample spacing), loss and gradient rounded
+ * to fp32 once.  No atomics: bitwise reproducible.
+ * packed: samples (M,) with intervals [t_starts_i, t_ends_i]; ray r owns samples chunk_starts[r] .. + chunk_cnts[r]
+ *   (a range is cut at M; an empty ray gets loss 0).
+ * dense: w and t_vals (N, S), S >= 2, with the compositing's own intervals: s_i = t_i, d_i = max(t_{i+1} - t_i, 1e-4)
+ *   and the last d copied from its predecessor (acn_volume_render_fwd's dists).
+ * ray_scale (N) or NULL: scale_r (mip-NeRF normalises a ray to unit length with 1 / (far - near); the loss is linear
+ *   in a common scale of m and d).  A ray whose scale is exactly 0.0f is skipped: zeros are written and its t values
+ *   are not read (an invalid ray with NaN near / far costs nothing and poisons nothing).
+ * grad_w (M) / (N, S) or NULL (loss only; the same loss bits).  N == 0 is a no-op. */
+int acn_distortion_packed(const float* weights, const float* t_starts, const float* t_ends, int64_t M,
+                          const int64_t* chunk_starts, const int64_t* chunk_cnts, int64_t N, const float* ray_scale,
+                          float* loss, float* grad_w, void* stream);
+int acn_distortion_dense(const float* weights, const float* t_vals, int64_t N, int S, const float* ray_scale,
+                         float* loss, float* grad_w, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Episodic task routing (data.hip).  Replaces TaskDataset's region clip + micro-cell assignment
