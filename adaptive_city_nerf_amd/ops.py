@@ -904,6 +904,50 @@ def distortion_dense(weights: torch.Tensor, t_vals: torch.Tensor, ray_scale: Opt
     return loss, grad
 
 
+RESAMPLE_MAX_S, RESAMPLE_MAX_F = 1024, 1024   # acn_resample_pdf's row limits (its LDS: 16 KB per ray)
+
+
+def resample_pdf(weights: torch.Tensor, t_vals: torch.Tensor, n_fine: int, jitter: Optional[torch.Tensor] = None,
+                 rays: Optional[torch.Tensor] = None, want_points: bool = False):
+    """(t_fine (N, F), t_merged (N, S + F), pts6 (N * (S + F), 6) or None) of classic NeRF's importance resampling
+    (acn_resample_pdf): F = ``n_fine`` depths per ray by the inverse CDF of the inner weights + 1e-5 over the bins
+    between the midpoints of ``t_vals``, at the stratified quantiles (j + jitter[n, j]) / F (0.5 without jitter), the
+    row merged with ``t_vals`` (a coarse sample before an equal fine one) and, with ``want_points``, the rows
+    [o + d t, d] of ``rays`` (N, 8).  One launch; float64 arithmetic, one fp32 rounding per depth; bitwise reproducible.
+    3 <= S <= 1024, 1 <= F <= 1024."""
+    if weights.dim() != 2 or weights.shape[1] < 3 or t_vals.shape != weights.shape:
+        raise AcnError(f"resample_pdf: weights and t_vals must both be (N, S >= 3), got {tuple(weights.shape)} and "
+                       f"{tuple(t_vals.shape)}")
+    F = int(n_fine)
+    if F < 1:
+        raise AcnError(f"resample_pdf: n_fine must be >= 1, got {n_fine}")
+    require_hip(weights, "resample_pdf")
+    wv, tv = _f32(weights), _f32(t_vals)
+    if tv.device != wv.device:
+        raise AcnError("resample_pdf: t_vals must be on the weights' device")
+    N, S = wv.shape
+    jit = None
+    if jitter is not None:
+        jit = _f32(jitter)
+        if jit.shape != (N, F) or jit.device != wv.device:
+            raise AcnError(f"resample_pdf: jitter must be ({N}, {F}) on the weights' device, got {tuple(jitter.shape)} "
+                           f"on {jitter.device}")
+    rv = None
+    if want_points:
+        if rays is None:
+            raise AcnError("resample_pdf: want_points needs the rays")
+        rv = _f32(rays)
+        if rv.dim() != 2 or rv.shape != (N, 8) or rv.device != wv.device:
+            raise AcnError(f"resample_pdf: rays must be ({N}, 8) on the weights' device, got {tuple(rays.shape)} on "
+                           f"{rays.device}")
+    t_fine = torch.empty(N, F, device=wv.device, dtype=torch.float32)
+    t_merged = torch.empty(N, S + F, device=wv.device, dtype=torch.float32)
+    pts6 = torch.empty(N * (S + F), 6, device=wv.device, dtype=torch.float32) if want_points else None
+    check(_lib.lib().acn_resample_pdf(ptr(wv), ptr(tv), N, int(S), ptr(jit), F, ptr(rv), ptr(t_fine), ptr(t_merged),
+                                      ptr(pts6), stream_of(wv)), "acn_resample_pdf")
+    return t_fine, t_merged, pts6
+
+
 def sample_stratified(rays: torch.Tensor, S: int, jitter: Optional[torch.Tensor], aabb_min, aabb_extent,
                       eps: float):
     """Training-path sampler (acn_sample_stratified): t_vals (N,S), x01 (N*S,3) in the expert's unit box

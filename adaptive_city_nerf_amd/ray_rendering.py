@@ -657,8 +657,143 @@ def render_rays_occ(model, rays: Tensor, *, params=None, bg_color_default: str =
                              bg_color_default)
 
 
+# ============================== Hierarchical (coarse to fine) rendering ===============================
+FUSED_RESAMPLE = True   # sample_pdf on acn_resample_pdf; tests switch it off to take the torch chain
+
+
+def _sample_pdf_torch(t_vals: Tensor, weights: Tensor, n_importance: int, jitter: Optional[Tensor] = None):
+    """(t_fine, t_merged) of sample_pdf as torch ops: acn_resample_pdf's definition in float64, every depth rounded to
+    fp32 once (CPU tensors, other dtypes, rows beyond the kernel's limits)."""
+    N, S = t_vals.shape
+    F = int(n_importance)
+    t, w = t_vals.detach().double(), weights.detach().double()
+    b = (t[:, :-1] + t[:, 1:]) / 2                                        # (N, S-1) edges
+    c = torch.cat([t.new_zeros(N, 1), torch.cumsum(w[:, 1:-1] + 1e-5, dim=1)], dim=1)   # (N, S-1), not normalised
+    r = 0.5 if jitter is None else jitter.detach().to(t.device, torch.float64)
+    v = ((torch.arange(F, device=t.device, dtype=torch.float64)[None, :] + r) / F) * c[:, -1:]
+    v = v.expand(N, F).contiguous()
+    k = (torch.searchsorted(c[:, :-1].contiguous(), v, right=True) - 1).clamp(0, S - 3)
+    c0, c1 = torch.gather(c, 1, k), torch.gather(c, 1, k + 1)
+    b0, b1 = torch.gather(b, 1, k), torch.gather(b, 1, k + 1)
+    den = c1 - c0
+    f = torch.where(den > 0, (v - c0) / den, torch.zeros_like(v)).clamp(0.0, 1.0)
+    t_fine = (b0 + f * (b1 - b0)).float().to(t_vals.dtype)
+    t_merged = torch.sort(torch.cat([t_vals.detach(), t_fine], dim=1), dim=1, stable=True).values
+    return t_fine, t_merged
+
+
+def _points6(rays: Tensor, t: Tensor) -> Tensor:
+    """The (N*S, 6) rows [o + d t, d] the model's forward takes (the composed path's expression)."""
+    o, d = rays[:, :3], rays[:, 3:6]
+    pts = o.unsqueeze(1) + d.unsqueeze(1) * t.unsqueeze(-1)
+    return torch.cat([pts, d.unsqueeze(1).expand_as(pts)], dim=-1).reshape(-1, 6)
+
+
+@torch.no_grad()
+def sample_pdf(t_vals: Tensor, weights: Tensor, n_importance: int, jitter: Optional[Tensor] = None, *,
+               return_merged: bool = False, rays: Optional[Tensor] = None):
+    """Classic NeRF's importance resampling: ``n_importance`` new depths per ray, (N, F), drawn by the inverse CDF of
+    the piecewise-constant density that ``weights[:, 1:-1] + 1e-5`` puts on the bins between the midpoints of
+    ``t_vals`` (both (N, S >= 3): the weights and t values of ``render_rays_stratified(..., return_t_vals=True)``), at
+    the stratified quantiles (j + jitter[n, j]) / F; ``jitter`` (N, F) in [0, 1), None = 0.5 (deterministic).  The
+    depths are non-decreasing along a ray and lie between the first and the last midpoint.
+
+    ``return_merged`` also returns the (N, S + F) sorted union with ``t_vals`` (a coarse sample before an equal fine
+    one), what ``volume_render`` and ``distortion_loss`` take; ``rays`` (N, 8), an extension, appends the
+    (N * (S + F), 6) rows [o + d t, d] of the merged depths and implies ``return_merged``.
+
+    No gradient: the weights are detached and the outputs are constants, as every t value here.  HIP fp32 tensors with
+    S <= 1024 and F <= 1024 take one launch (acn_resample_pdf: float64 arithmetic, one fp32 rounding per depth);
+    everything else the same definition as torch ops."""
+    if t_vals.dim() != 2 or t_vals.shape[1] < 3 or weights.shape != t_vals.shape:
+        raise ops.AcnError(f"sample_pdf: t_vals and weights must both be (N, S >= 3), got {tuple(t_vals.shape)} and "
+                           f"{tuple(weights.shape)}")
+    F = int(n_importance)
+    if F < 1:
+        raise ops.AcnError(f"sample_pdf: n_importance must be >= 1, got {n_importance}")
+    N, S = t_vals.shape
+    if jitter is not None and tuple(jitter.shape) != (N, F):
+        raise ops.AcnError(f"sample_pdf: jitter must be ({N}, {F}), got {tuple(jitter.shape)}")
+    if rays is not None and (rays.dim() != 2 or rays.shape[0] != N or rays.shape[1] < 8):
+        raise ops.AcnError(f"sample_pdf: rays must be ({N}, >=8), got {tuple(rays.shape)}")
+    fused = (FUSED_RESAMPLE and t_vals.is_cuda and t_vals.dtype == torch.float32 and weights.dtype == torch.float32
+             and S <= ops.RESAMPLE_MAX_S and F <= ops.RESAMPLE_MAX_F and (rays is None or rays.dtype == torch.float32))
+    if fused:
+        jit = None if jitter is None else jitter.to(t_vals.device)
+        t_fine, t_merged, pts6 = ops.resample_pdf(weights, t_vals, F, jitter=jit,
+                                                  rays=None if rays is None else rays.detach()[:, :8],
+                                                  want_points=rays is not None)
+    else:
+        t_fine, t_merged = _sample_pdf_torch(t_vals, weights, F, jitter)
+        pts6 = None if rays is None else _points6(rays.detach(), t_merged)
+    if rays is not None:
+        return t_fine, t_merged, pts6
+    return (t_fine, t_merged) if return_merged else t_fine
+
+
+def render_rays_hierarchical(model, rays: Tensor, ray_samples: int, n_importance: int, params=None,
+                             active_module: Optional[int] = None, bg_color_default: str = "white", sigma_scale=1.0,
+                             return_coarse: bool = False, return_t_vals: bool = False, **kwargs):
+    """Coarse-to-fine stratified renderer (classic NeRF): a coarse pass of ``ray_samples`` depths
+    (render_rays_stratified), ``n_importance`` further depths per ray where the coarse weights are (sample_pdf), and the
+    model evaluated once more on the S + F merged depths.  Returns the fine pass: rgb (N,3), depth (N,), weights
+    (N, S+F), acc (N,).
+
+    The coarse pass runs without autograd (in eval mode it is the fused render) unless ``return_coarse``, which
+    appends its differentiable (rgb, depth, weights, acc) as one tuple, for the coarse-plus-fine loss.
+    ``return_t_vals`` appends the merged (N, S+F) depths last (``distortion_loss(weights, t_merged, rays)``).  The
+    resampling carries no gradient.  In training mode the fine quantiles are jittered by ``jitter_fine`` (N, F) or
+    torch.rand; in eval mode they are the bin centres.  ``jitter_u``, ``early_stop_tau`` and ``chunk`` go to the coarse
+    pass as in render_rays_stratified.  Rays that require grad are differentiated through the fine pass's points."""
+    F = int(n_importance)
+    if F < 1:
+        raise ops.AcnError(f"render_rays_hierarchical: n_importance must be >= 1, got {n_importance}")
+    if int(ray_samples) < 3:
+        raise ops.AcnError(f"render_rays_hierarchical: the coarse pass needs ray_samples >= 3, got {ray_samples}")
+    chunk = int(kwargs.pop("chunk", 1_000_000))
+    jitter_fine = kwargs.pop("jitter_fine", None)
+    kwargs.pop("_want_weights", None)   # the resampling needs the coarse weights whatever the caller keeps
+    N = rays.shape[0]
+    with torch.enable_grad() if return_coarse and torch.is_grad_enabled() else torch.no_grad():
+        coarse = render_rays_stratified(model, rays, ray_samples, params=params, active_module=active_module,
+                                        bg_color_default=bg_color_default, chunk=chunk, sigma_scale=sigma_scale,
+                                        return_t_vals=True, **kwargs)
+    w_c, t_c = coarse[2].detach(), coarse[4].detach()
+    jitter = None
+    if model.training:
+        jitter = jitter_fine if jitter_fine is not None else torch.rand(N, F, device=rays.device)
+    if wants_grad(rays):   # the points carry the rays' gradient: the torch expression, not the kernel's constants
+        _, t_merged = sample_pdf(t_c, w_c, F, jitter, return_merged=True)
+        id6 = _points6(rays, t_merged)
+    else:
+        _, t_merged, id6 = sample_pdf(t_c, w_c, F, jitter, rays=rays)
+    model_eff = model.submodules[active_module] if active_module is not None else model
+    outs = [model_eff(id6[s: s + chunk], params=params) for s in range(0, id6.shape[0], chunk)]
+    rgb_sigma = torch.cat(outs, dim=0).view(N, t_merged.shape[1], 4)
+    bg_rgb = _get_bg_rgb(model, rays[:, 3:6], params, rgb_sigma, N=N, bg_color_default=bg_color_default)
+    out = volume_render(rgb_sigma, t_merged, bg_rgb=bg_rgb, raw_rgb=False, raw_sigma=False, sigma_scale=sigma_scale)
+    if return_coarse:
+        out += (tuple(coarse[:4]),)
+    return out + (t_merged,) if return_t_vals else out
+
+
+_STRATIFIED_POSITIONALS = ("ray_samples", "params", "active_module", "bg_color_default", "chunk", "sigma_scale",
+                           "return_t_vals")
+
+
 def render_rays(model, rays, *args, **kwargs):
-    """Entry point (:564-574): occupancy renderer once the model's grids are ready, else stratified."""
+    """Entry point (:564-574): occupancy renderer once the model's grids are ready, else stratified.
+    ``n_importance`` = K > 0 (an extension) renders coarse to fine (render_rays_hierarchical) with K further depths
+    per ray; it is an error once the occupancy renderer is active, which concentrates its samples by marching."""
+    n_importance = int(kwargs.pop("n_importance", 0) or 0)
+    if n_importance > 0:
+        if getattr(model, "use_occ", False) and model.occ_ready:
+            raise ops.AcnError("render_rays(n_importance > 0): the occupancy renderer concentrates its samples by "
+                               "marching; importance resampling goes with the stratified renderer")
+        if len(args) > len(_STRATIFIED_POSITIONALS):
+            raise TypeError("render_rays: too many positional arguments")
+        kwargs.update(zip(_STRATIFIED_POSITIONALS, args))   # render_rays_stratified's positional order
+        return render_rays_hierarchical(model, rays, kwargs.pop("ray_samples"), n_importance, **kwargs)
     if getattr(model, "use_occ", False):
         if not model.occ_ready:
             return render_rays_stratified(model, rays, *args, **kwargs)

@@ -90,6 +90,8 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
                **render_kwargs) -> torch.Tensor:
     """One optimizer update of runtime_adapt (runtime_adapt.py:288-313).  Returns the loss (device).
     ``distortion_weight`` > 0 adds that multiple of the mean distortion loss (compute_loss) to the MSE.
+    ``n_importance`` = K > 0 (through ``render_kwargs``, with ``jitter_fine``) trains on the coarse-to-fine render
+    (render_rays_hierarchical): the loss is taken on the fine pass.
 
     ``group`` (expert parallel): ``rays`` / ``rgbs`` are this rank's shard of the global batch, the
     container's experts are distributed over the group (expert_parallel.adapt_step_expert_parallel);
@@ -99,6 +101,9 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
     None) scales the loss, unscales, skips a non-finite step and updates its scale."""
     if group is not None and distortion_weight:
         raise ValueError("adapt_step: the expert-parallel step has no distortion loss (distortion_weight must be 0 "
+                         "with a group)")
+    if group is not None and render_kwargs.get("n_importance"):
+        raise ValueError("adapt_step: the expert-parallel step renders one stratified pass (n_importance must be 0 "
                          "with a group)")
     if group is not None and torch.distributed.is_initialized() and torch.distributed.get_world_size(group) > 1:
         from .expert_parallel import HipBackend, adapt_step_expert_parallel
@@ -149,6 +154,9 @@ class GraphedAdaptStep:
     def __init__(self, P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Optional[float] = 1.0,
                  warmup: int = 2, max_steps: int = 1 << 16, distortion_weight: float = 0.0, **render_kwargs):
         from .meta_container import MetaContainer
+        if render_kwargs.get("n_importance"):
+            raise ValueError("GraphedAdaptStep: the hierarchical render (n_importance > 0) is not captured; use "
+                             "adapt_step")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedAdaptStep needs FusedAdam")
         if isinstance(base, MetaContainer) and active_module is None:

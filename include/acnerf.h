@@ -602,6 +602,27 @@ int acn_distortion_packed(const float* weights, const float* t_starts, const flo
                           float* loss, float* grad_w, void* stream);
 int acn_distortion_dense(const float* weights, const float* t_vals, int64_t N, int S, const float* ray_scale,
                          float* loss, float* grad_w, void* stream);
+/* Hierarchical importance resampling (classic NeRF sample_pdf) of the weights of a coarse pass, in one launch: F new
+ * depths per ray by the inverse CDF of the piecewise-constant density the inner weights describe, the row merged with
+ * the coarse depths and, optionally, the sample points.  Per ray, in float64 on the fp32 inputs (t_vals non-decreasing,
+ * weights >= 0):
+ *   edges b_i = (t_i + t_{i+1}) / 2 (i = 0 .. S-2); bin masses p_i = w_{i+1} + 1e-5 (i = 0 .. S-3: weights[1:-1] +
+ *   1e-5, so a ray of zero weights resamples uniformly); c_0 = 0, c_k = p_0 + .. + p_{k-1}, C = c_{S-2} (no division by
+ *   C); v_j = (j + r_j) / F * C with r_j = jitter[n, j] in [0, 1), or 0.5 when jitter is NULL (stratified quantiles,
+ *   ascending by construction); k the largest index in [0, S-3] with c_k <= v_j; f = clamp((v_j - c_k) /
+ *   (c_{k+1} - c_k), 0, 1), 0 when the denominator is not positive; t_fine_j = b_k + f (b_{k+1} - b_k) rounded to fp32
+ *   once: non-decreasing along a row, inside [b_0, b_{S-2}].
+ * t_merged (N, S+F): the stable merge of t_vals with t_fine, a coarse sample before an equal fine one (coarse i goes to
+ *   i + #{fine < t_i}, fine j to j + #{coarse <= x_j}: no sort).
+ * pts6 (N*(S+F), 6) or NULL: row (n, m) = [o + d * t_merged[n, m], d] from rays (N, 8) = [o, d, near, far], the
+ *   product and the sum rounded separately (the torch expression's bits).  t_fine (N, F) or NULL.  The outputs do not
+ *   depend on which optional ones are requested.
+ * One wave per ray, the CDF a float64 wave scan, every binary search a fixed number of steps inside the ray's own
+ * arrays: a row that breaks the preconditions (NaN or unsorted t) may hold garbage, but only its own row; no atomics,
+ * bitwise reproducible.  3 <= S <= 1024 and 1 <= F <= 1024, else ACN_ERR_UNSUPPORTED before any HIP call.  N == 0 is a
+ * no-op. */
+int acn_resample_pdf(const float* weights, const float* t_vals, int64_t N, int S, const float* jitter, int F,
+                     const float* rays, float* t_fine, float* t_merged, float* pts6, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Episodic task routing (data.hip).  Replaces TaskDataset's region clip + micro-cell assignment
