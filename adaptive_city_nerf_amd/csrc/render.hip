@@ -24,6 +24,9 @@
 //                        (16-ray rounds up to S = 128, else 8-ray rounds)
 //   render_slots_kernel  routed K > 2 otherwise: one wave per ray over two LDS expert slots
 //   occ_render_kernel    packed (occupancy-grid) samples: one wave per ray
+// acn_render_depths_fwd (caller-supplied depths) launches the TV instantiations of the two
+// one-wave-per-ray kernels: render_kernel<.., true> for one expert and routed K == 2, render_slots_kernel<.., true>
+// for routed K > 2 (fp32 tables only).
 //
 // Build switches that remain (every other A/B of rounds 2-6 is settled and gone; DESIGN.md §4 keeps the figures):
 //   ACN_MLP_F16X3      0: the exact-fp32 MLP on v_mfma_f32_32x32x2_f32, the documented escape hatch
@@ -881,7 +884,7 @@ struct RenderParams {
     const float* rays;
     int64_t N;
     int32_t S;
-    const float* jitter;
+    const float* jitter;   // the explicit-depth instantiations (TV): the (N, S) depths themselves, not uniforms
     const float* packed;
     float sigma_scale, tau;
     float *rgb, *depth, *weights, *acc;
@@ -935,6 +938,16 @@ __device__ __forceinline__ float sample_t_dist(float near, float far, int sc, in
     return t;
 }
 
+// Explicit depths (the TV instantiations, acn_render_depths_fwd): t and dist of sample sc < S from the ray's row
+// of caller-supplied depths, volume_render's rule (dist = t[i+1] - t[i], the last one repeated).  Both loads stay
+// inside the row for every sc in [0, S), S >= 2; the values are not looked at (no index depends on one).
+__device__ __forceinline__ float row_t_dist(const float* __restrict__ row, int sc, int S, float& dist) {
+    const int i0 = sc < S - 1 ? sc : S - 2;
+    const float ta = row[i0], tb = row[i0 + 1];
+    dist = tb - ta;
+    return sc < S - 1 ? ta : tb;
+}
+
 // The end of a ray: background, the double reductions of the per-lane partials, the background blend, the outputs
 __device__ __forceinline__ void finish_and_store(const RayAcc& acc, const BgArgs& bg, float dx, float dy, float dz,
                                                  int lane, int64_t ray, const RenderParams& p) {
@@ -979,8 +992,9 @@ __device__ __forceinline__ void xcd_band(int64_t n, int64_t per, int64_t& first,
 // One ray, front to back in 32-sample tiles: t-values -> field(px, py, pz, shv, folded, y...) ->
 // volume_render conditioning -> compositing -> background -> outputs.  `field` evaluates the
 // (routed) container for this lane's sample; it is a template callable so the single-expert, the
-// LDS-resident and the slot-staged kernels share this body.
-template <class FieldFn>
+// LDS-resident and the slot-staged kernels share this body.  TV: the depths are read from the ray's row of
+// p.jitter (row_t_dist) instead of being computed from near / far, which are then unused.
+template <bool TV = false, class FieldFn>
 __device__ __forceinline__ void render_ray(const RenderParams& p, const BgArgs& bg, int64_t ray, int lane, float step,
                                            FieldFn&& field) {
     const int j = lane & 31, h = lane >> 5;
@@ -996,8 +1010,9 @@ __device__ __forceinline__ void render_ray(const RenderParams& p, const BgArgs& 
         const int s = s0 + j;
         const bool valid = s < S;
         const int sc = valid ? s : S - 1;
-        float dist;
-        const float t = sample_t_dist(r.near, r.far, sc, S, step, r.jit, dist);
+        float dist, t;
+        if constexpr (TV) t = row_t_dist(r.jit, sc, S, dist);
+        else t = sample_t_dist(r.near, r.far, sc, S, step, r.jit, dist);
         const float px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;
         float yr, yg, yb, ys;
         field(sc, px, py, pz, shv, folded, yr, yg, yb, ys);
@@ -1018,7 +1033,7 @@ __device__ __forceinline__ void render_ray(const RenderParams& p, const BgArgs& 
     finish_and_store(acc, bg, r.dx, r.dy, r.dz, lane, ray, p);
 }
 
-template <int INTERP, int KL, int ROUTE>
+template <int INTERP, int KL, int ROUTE, bool TV = false>
 __global__ void __launch_bounds__(1024, 4) render_kernel(FieldCfg cfg, BgArgs bg, RenderParams p) {
     constexpr int KF = ROUTE == 0 ? 1 : (KL == 2 ? 2 : kMaxK);  // experts a ray may fold
     __shared__ __attribute__((aligned(16))) float smem[(KL > 0 ? KL : 1) * PK_FLOATS];
@@ -1036,7 +1051,7 @@ __global__ void __launch_bounds__(1024, 4) render_kernel(FieldCfg cfg, BgArgs bg
     xcd_band(p.N, blockDim.x >> 6, pos, hi, stride);
     for (pos += wave; pos < hi; pos += stride) {
         const int64_t ray = p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[pos]) : pos;
-        render_ray(p, bg, ray, lane, step,
+        render_ray<TV>(p, bg, ray, lane, step,
                    [&](int, float px, float py, float pz, const float (&shv)[8], uint32_t& folded, float& yr, float& yg,
                        float& yb, float& ys) {
                        container_tile<INTERP, ROUTE, true>(cfg, W, px, py, pz, shv, cb, &folded, lane, yr, yg, yb, ys);
@@ -1239,6 +1254,7 @@ __device__ __forceinline__ void soft_route_bits(const FieldCfg& cfg, float px, f
         exact = exact && (inv / den == 1.0f);
     }
 }
+template <bool TV = false>   // TV: the ray's row of explicit depths (render_ray)
 __device__ __forceinline__ uint32_t ray_expert_mask(const FieldCfg& cfg, int route, const RenderParams& p, int64_t ray,
                                                     bool live, float step, int lane) {
     uint32_t m = 0u;
@@ -1246,7 +1262,9 @@ __device__ __forceinline__ uint32_t ray_expert_mask(const FieldCfg& cfg, int rou
     if (live) {
         const RayIn r = load_ray(p, ray);
         for (int s = lane; s < p.S; s += 64) {
-            const float t = r.jit ? tval(r.near, r.far, s, p.S, r.jit) : tlin_sel(r.near, r.far, s, p.S, step);
+            float t;
+            if constexpr (TV) t = r.jit[s];
+            else t = r.jit ? tval(r.near, r.far, s, p.S, r.jit) : tlin_sel(r.near, r.far, s, p.S, step);
             const float px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;
             if (route == 1) {
                 soft_route_bits(cfg, px, py, pz, m, exact);
@@ -1380,7 +1398,7 @@ __device__ __forceinline__ void slots_field(const FieldCfg& cfg, const RenderPar
     }
 }
 
-template <int INTERP, int ROUTE>
+template <int INTERP, int ROUTE, bool TV = false>
 __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) render_slots_kernel(FieldCfg cfg, BgArgs bg, RenderParams p) {
     __shared__ __attribute__((aligned(16))) float smem[2 * PK_FLOATS];
     // per wave: the folded SH bias of the two LDS slots and of the expert read from L2 (every expert's
@@ -1408,7 +1426,7 @@ __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) re
         const bool live = base + wave < lim;
         const int64_t ray = !live ? 0 : (p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[base + wave])
                                                  : base + wave);
-        const uint32_t m = ray_expert_mask(cfg, ROUTE, p, ray, live, step, lane);
+        const uint32_t m = ray_expert_mask<TV>(cfg, ROUTE, p, ray, live, step, lane);
         int* cq = cnt[rbuf];
         if (lane == 0)
             for (int k = 0; k < cfg.K; ++k)
@@ -1422,7 +1440,7 @@ __global__ void __launch_bounds__(ACN_SLOTS_THREADS, ACN_SLOTS_THREADS / 256) re
         if (live) {
             const bool single = (m & kSingleRay) != 0u;
             const int k_single = __builtin_ctz(m | kSingleRay);
-            render_ray(p, bg, ray, lane, step,
+            render_ray<TV>(p, bg, ray, lane, step,
                        [&](int sc_, float px, float py, float pz, const float (&shv)[8], uint32_t& folded, float& yr, float& yg,
                            float& yb, float& ys) {
                            (void)sc_;
@@ -2662,6 +2680,52 @@ extern "C" int acn_render_stratified_fwd_ordered(const float* rays, int64_t N, i
     ACN_DISPATCH_FMT(ACN_RENDER_LAUNCH);
 #undef ACN_RENDER_LAUNCH
     return acn_check_launch("acn_render_stratified_fwd");
+}
+
+namespace {
+// The explicit-depth render's kernel: the one-wave-per-ray kernels' TV instantiations (early termination included;
+// the depth-tiled kernels compute their own depths)
+template <int I, int KL, int R>
+void launch_render_depths(dim3 grid, hipStream_t s, const FieldCfg& cfg, const BgArgs& b, const RenderParams& p) {
+    if constexpr (KL == 0)
+        hipLaunchKernelGGL((render_slots_kernel<I, R, true>), grid, dim3(ACN_SLOTS_THREADS), 0, s, cfg, b, p);
+    else
+        hipLaunchKernelGGL((render_kernel<I, KL, R, true>), grid, dim3(1024), 0, s, cfg, b, p);
+}
+}  // namespace
+
+extern "C" int acn_render_depths_fwd(const float* rays, int64_t N, int S, const float* t_vals,
+                                     const acn_expert* experts, const acn_routing* routing, int active_module,
+                                     const acn_background* bg, float sigma_scale, float tau, void* workspace,
+                                     size_t workspace_bytes, float* rgb, float* depth, float* weights, float* acc,
+                                     void* order_scratch, size_t order_bytes, void* stream) {
+    ACN_REQUIRE(N >= 0, "acn_render_depths_fwd: N must be >= 0");
+    ACN_REQUIRE(S >= 2, "acn_render_depths_fwd: t_vals must hold S >= 2 depths per ray, got %d", S);
+    if (N == 0) return ACN_OK;
+    ACN_REQUIRE(rays && t_vals && rgb && depth && acc, "acn_render_depths_fwd: NULL pointer");
+    ACN_REQUIRE(bg, "acn_render_depths_fwd: NULL background");
+    if (bg->mode == ACN_BG_MLP) {
+        ACN_REQUIRE(bg->w1 && bg->b1 && bg->w2 && bg->b2, "background MLP pointers are NULL");
+        ACN_REQUIRE(bg->hidden >= 1 && bg->hidden <= 64, "bg_hidden must be in [1, 64], got %d", bg->hidden);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    FieldCfg cfg{};
+    int interp, K;
+    int st = prepare(experts, routing, active_module, workspace, workspace_bytes, s, cfg, interp, K, false);
+    if (st) return st;   // an fp16 expert included: only the fp32 families have TV instantiations
+    BgArgs b{bg->mode, bg->hidden, {bg->color[0], bg->color[1], bg->color[2]}, bg->w1, bg->b1, bg->w2, bg->b2};
+    // the depths travel in RenderParams::jitter: the TV instantiations read nothing else from it
+    RenderParams p{rays, N, S, t_vals, (const float*)workspace, sigma_scale, tau, rgb, depth, weights, acc, nullptr};
+    const dim3 grid = render_grid(N);
+    const bool slots = cfg.routing != 0 && K != 2;  // render_slots_kernel keeps its own order
+    if (order_scratch && !slots && N <= ACN_ORDER_MAX && order_bytes >= (size_t)N * sizeof(int32_t)) {
+        hipLaunchKernelGGL(ray_order_kernel, dim3(1), dim3(1024), 0, s, rays, (int)N, (int32_t*)order_scratch);
+        p.order = (const int32_t*)order_scratch;
+    }
+#define ACN_RENDER_LAUNCH(I, KL, R) launch_render_depths<I, KL, R>(grid, s, cfg, b, p)
+    ACN_DISPATCH(ACN_RENDER_LAUNCH);
+#undef ACN_RENDER_LAUNCH
+    return acn_check_launch("acn_render_depths_fwd");
 }
 
 extern "C" int acn_volume_render_fwd(const float* rgb_sigma, const float* t_vals, const float* bg, int64_t N, int S,

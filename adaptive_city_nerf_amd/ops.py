@@ -404,6 +404,54 @@ def render_stratified(rays: torch.Tensor, S: int, experts: Sequence[ExpertSpec],
     return rgb, depth, weights, acc
 
 
+def _is_f16_expert(e: ExpertSpec) -> bool:
+    return int(e.s.table_fmt) == _lib.ACN_TABLE_F16
+
+
+def render_depths(rays: torch.Tensor, t_vals: torch.Tensor, experts: Sequence[ExpertSpec], routing: acn_routing,
+                  active_module: Optional[int], background, sigma_scale: float = 1.0, tau: float = 0.0,
+                  want_weights: bool = True, packed: Optional[torch.Tensor] = None, reorder: Optional[bool] = None):
+    """render_stratified at the caller's depths: sample s of ray n at ``t_vals[n, s]`` ((N, S >= 2), non-decreasing
+    along a ray; near / far of the rays are not read), one fused launch (acn_render_depths_fwd).  The depths are
+    not validated: a NaN or unsorted row spoils that ray's outputs only.  fp32 hash tables only."""
+    assert rays.dim() == 2 and rays.shape[-1] == 8, "rays must be (N,8)"
+    N = rays.shape[0]
+    if t_vals.dim() != 2 or t_vals.shape[0] != N or t_vals.shape[1] < 2:
+        raise AcnError(f"render_depths: t_vals must be ({N}, S >= 2), got {tuple(t_vals.shape)}")
+    require_hip(rays, "render_depths")
+    if t_vals.device != rays.device:
+        raise AcnError(f"render_depths: t_vals is on {t_vals.device}, the rays on {rays.device}")
+    if any(_is_f16_expert(e) for e in experts):
+        raise AcnError("render_depths: fp16 hash tables are rendered by render_stratified only; pass the fp32 experts")
+    r = _f32(rays)
+    t = _f32(t_vals)
+    S = t.shape[1]
+    dev = r.device
+    rgb = torch.empty(N, 3, device=dev, dtype=torch.float32)
+    depth = torch.empty(N, device=dev, dtype=torch.float32)
+    acc = torch.empty(N, device=dev, dtype=torch.float32)
+    weights = torch.empty(N, S, device=dev, dtype=torch.float32) if want_weights else None
+    if N == 0:
+        return rgb, depth, weights, acc
+    ws = packed if packed is not None else pack_experts(experts, routing, active_module)
+    arr = _experts_array(experts)
+    obytes = int(_lib.lib().acn_render_order_bytes(N)) if (REORDER if reorder is None else reorder) else 0
+    order = torch.empty(obytes // 4, device=dev, dtype=torch.int32) if obytes else None
+    hook = EVENT_HOOK
+    if hook is not None:
+        e0 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(_lib.lib().acn_render_depths_fwd(
+        ptr(r), N, int(S), ptr(t), arr, C.byref(routing), -1 if active_module is None else int(active_module),
+        C.byref(background), float(sigma_scale), float(tau), ptr(ws), ws.numel() * 4, ptr(rgb), ptr(depth),
+        ptr(weights), ptr(acc), ptr(order), obytes, stream_of(r)), "acn_render_depths_fwd")
+    if hook is not None:
+        e1 = torch.cuda.Event(enable_timing=True)
+        e1.record()
+        hook.append((e0, e1))
+    return rgb, depth, weights, acc
+
+
 def volume_render(rgb_sigma: torch.Tensor, t_vals: torch.Tensor, bg_rgb: Optional[torch.Tensor] = None,
                   raw_rgb: bool = False, raw_sigma: bool = False, sigma_scale: float = 1.0):
     require_hip(rgb_sigma, "volume_render")

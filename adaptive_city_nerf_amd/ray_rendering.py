@@ -731,6 +731,74 @@ def sample_pdf(t_vals: Tensor, weights: Tensor, n_importance: int, jitter: Optio
     return (t_fine, t_merged) if return_merged else t_fine
 
 
+FUSED_FINE_RENDER = True   # render_rays_hierarchical's fine pass on render_rays_at's fused launch;
+                           # tests switch it off to take the composed chain
+
+
+def _f16_render_tables(model) -> bool:
+    """An expert of the model renders from an fp16 table (set_render_table_dtype): its no-grad forward then reads
+    that table, which the explicit-depth kernels do not."""
+    subs = model.submodules if isinstance(model, MetaContainer) else [model]
+    return any(getattr(getattr(s, "xyz_encoder", None), "render_table_dtype", torch.float32) == torch.float16
+               for s in subs)
+
+
+def _fused_depths(model, rays: Tensor, t_vals: Tensor, params, active_module, bg_color_default: str):
+    """(specs, routing, packed, background, keep) when a render at the depths ``t_vals`` can take the fused launch
+    (ops.render_depths), else None: render_rays_stratified's conditions, fp32 depths and fp32 hash tables."""
+    if not (rays.is_cuda and t_vals.is_cuda and t_vals.dtype == torch.float32) or wants_grad(rays):
+        return None
+    if _f16_render_tables(model):
+        return None
+    fe = _fused_experts(model, params, active_module)
+    fb = _fused_background(model, bg_color_default, rays.shape[0], rays.device) if fe is not None else None
+    if fe is None or fb is None:
+        return None
+    return fe + tuple(fb)
+
+
+def _render_depths_fused(rays: Tensor, t_vals: Tensor, fd, sigma_scale, tau: float):
+    specs, routing, packed, bg, keep = fd
+    rgb, depth, w, acc = ops.render_depths(rays, t_vals, specs, routing, 0 if len(specs) == 1 else None, bg,
+                                           sigma_scale=float(sigma_scale), tau=tau, packed=packed)
+    return rgb.to(rays.dtype), depth.to(rays.dtype), w.to(rays.dtype), acc.to(rays.dtype)
+
+
+def _check_depths(rays: Tensor, t_vals: Tensor, what: str) -> None:
+    N = rays.shape[0]
+    if t_vals.dim() != 2 or t_vals.shape[0] != N or t_vals.shape[1] < 2:
+        raise ops.AcnError(f"{what}: t_vals must be ({N}, S >= 2), got {tuple(t_vals.shape)}")
+    if t_vals.device != rays.device:
+        raise ops.AcnError(f"{what}: t_vals is on {t_vals.device}, the rays on {rays.device}")
+
+
+def render_rays_at(model, rays: Tensor, t_vals: Tensor, params=None, active_module: Optional[int] = None,
+                   bg_color_default: str = "white", chunk: int = 1_000_000, sigma_scale=1.0,
+                   early_stop_tau: float = 0.0):
+    """The stratified renderer at the caller's depths (an extension): sample s of ray n at ``t_vals[n, s]``, (N, S >= 2)
+    and non-decreasing along a ray, instead of the near..far linspace; near / far of the rays are not used.  Returns
+    rgb (N,3), depth (N,), weights (N,S), acc (N,).
+
+    HIP rays that do not require grad, fp32 depths and a model render_rays_stratified would render fused (no fast
+    weights that need grad, a background the kernel evaluates, no fp16 render table) take one launch
+    (ops.render_depths; ``early_stop_tau`` as in render_rays_stratified).  Everything else is the composed chain --
+    the points o + d t, the model's forward in ``chunk`` pieces, the background and ``volume_render`` -- which is also
+    the differentiable form (model parameters, fast weights, ray origins and directions).  ``t_vals`` is a constant:
+    it never carries a gradient.  The depths are not validated: a NaN or unsorted row spoils that ray only."""
+    _check_depths(rays, t_vals, "render_rays_at")
+    t_vals = t_vals.detach()
+    fd = _fused_depths(model, rays, t_vals, params, active_module, bg_color_default)
+    if fd is not None:
+        return _render_depths_fused(rays, t_vals, fd, sigma_scale, float(early_stop_tau))
+    N, S = t_vals.shape
+    id6 = _points6(rays, t_vals)
+    model_eff = model.submodules[active_module] if active_module is not None else model
+    outs = [model_eff(id6[s: s + chunk], params=params) for s in range(0, id6.shape[0], chunk)]
+    rgb_sigma = torch.cat(outs, dim=0).view(N, S, 4)
+    bg_rgb = _get_bg_rgb(model, rays[:, 3:6], params, rgb_sigma, N=N, bg_color_default=bg_color_default)
+    return volume_render(rgb_sigma, t_vals, bg_rgb=bg_rgb, raw_rgb=False, raw_sigma=False, sigma_scale=sigma_scale)
+
+
 def render_rays_hierarchical(model, rays: Tensor, ray_samples: int, n_importance: int, params=None,
                              active_module: Optional[int] = None, bg_color_default: str = "white", sigma_scale=1.0,
                              return_coarse: bool = False, return_t_vals: bool = False, **kwargs):
@@ -744,7 +812,10 @@ def render_rays_hierarchical(model, rays: Tensor, ray_samples: int, n_importance
     ``return_t_vals`` appends the merged (N, S+F) depths last (``distortion_loss(weights, t_merged, rays)``).  The
     resampling carries no gradient.  In training mode the fine quantiles are jittered by ``jitter_fine`` (N, F) or
     torch.rand; in eval mode they are the bin centres.  ``jitter_u``, ``early_stop_tau`` and ``chunk`` go to the coarse
-    pass as in render_rays_stratified.  Rays that require grad are differentiated through the fine pass's points."""
+    pass as in render_rays_stratified.  Rays that require grad are differentiated through the fine pass's points.
+
+    A fine pass that needs no gradient (render_rays_at's conditions for its fused launch) is that one launch at the
+    merged depths, without a point table, unless FUSED_FINE_RENDER is off; otherwise it is the composed chain."""
     F = int(n_importance)
     if F < 1:
         raise ops.AcnError(f"render_rays_hierarchical: n_importance must be >= 1, got {n_importance}")
@@ -762,6 +833,13 @@ def render_rays_hierarchical(model, rays: Tensor, ray_samples: int, n_importance
     jitter = None
     if model.training:
         jitter = jitter_fine if jitter_fine is not None else torch.rand(N, F, device=rays.device)
+    fd = _fused_depths(model, rays, t_c, params, active_module, bg_color_default) if FUSED_FINE_RENDER else None
+    if fd is not None:   # the fine pass in one launch at the merged depths: no point table (render_rays_at)
+        _, t_merged = sample_pdf(t_c, w_c, F, jitter, return_merged=True)
+        out = _render_depths_fused(rays, t_merged, fd, sigma_scale, 0.0)
+        if return_coarse:
+            out += (tuple(coarse[:4]),)
+        return out + (t_merged,) if return_t_vals else out
     if wants_grad(rays):   # the points carry the rays' gradient: the torch expression, not the kernel's constants
         _, t_merged = sample_pdf(t_c, w_c, F, jitter, return_merged=True)
         id6 = _points6(rays, t_merged)

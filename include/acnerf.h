@@ -250,6 +250,19 @@ int acn_render_stratified_fwd_ordered(const float* rays, int64_t N, int S, const
                                       float* depth, float* weights, float* acc, void* order_scratch,
                                       size_t order_bytes, void* stream);
 
+/* The fused render at caller-supplied depths: acn_render_stratified_fwd_ordered with sample s of ray n at
+ * t_vals[n * S + s] instead of the near..far linspace (columns 6-7 of rays are not read).  t_vals: (N, S >= 2)
+ * fp32, non-decreasing along a ray; dist = t[s+1] - t[s], the last one repeated (volume_render's rule, :144-145).
+ * The values are not validated: a row with NaN or unsorted depths yields garbage in that ray's outputs only.
+ * Early termination (tau > 0), weights (NULL = not written) and the visiting order as in the stratified call.
+ * fp32 hash tables only: an expert with table_fmt = ACN_TABLE_F16 returns ACN_ERR_UNSUPPORTED before any launch.
+ * N == 0 returns ACN_OK.                                                                                        */
+int acn_render_depths_fwd(const float* rays, int64_t N, int S, const float* t_vals,
+                          const acn_expert* experts, const acn_routing* routing, int active_module,
+                          const acn_background* bg, float sigma_scale, float tau, void* workspace,
+                          size_t workspace_bytes, float* rgb, float* depth, float* weights, float* acc,
+                          void* order_scratch, size_t order_bytes, void* stream);
+
 /* get_ray_directions + get_rays + clamp_rays_near_far (nerfs/ray_sampling.py:111-136, :50-108,
  * :139-176) with SceneBox.ray_aabb_intersect (nerfs/scene_box.py:45-107).  c2w: host (3,4)
  * row-major; aabb: host (2,3) or NULL (then near/far constants are used); the override flags
