@@ -126,6 +126,8 @@ def test_sh_bit_exact_vs_reference(levels):
 
 
 def test_volume_render_vs_reference():
+    """The golden's rays are dead by its second 32-sample tile and last sample, which it so cannot see: those, ragged
+    S and the grid-stride loop are pinned by tests/volume_render_ref.py and tests/test_volume_render_gpu.py."""
     ops = _ops()
     d = G.load("volume_render")
     rgb, depth, w, acc = ops.volume_render(_t(d["rgb_sigma"]), _t(d["t_vals"]), _t(d["bg"]))

@@ -226,7 +226,9 @@ def test_adapt_steps_match_reference_fixture(tag):
 def test_volume_render_backward_matches_autograd(with_bg, scale):
     """HIP compositing backward == torch autograd of the reference formulas (ray_rendering.py:137-165),
     evaluated in float64 on the CPU, on the reference's volume_render fixture inputs (incl. saturated
-    rays, clamped rgb, sigma < 0 and a sub-1e-4 step)."""
+    rays, clamped rgb, sigma < 0 and a sub-1e-4 step).  That fixture (two full tiles, weights below 5e-3 past sample 48, all four
+    output gradients) cannot see the second tile, the last sample or the NULL-gradient branches: those are pinned by
+    tests/volume_render_ref.py and tests/test_volume_render_gpu.py."""
     from adaptive_city_nerf_amd.ray_rendering import _volume_render_autograd, volume_render
     d = G.load("volume_render")
     rs = torch.from_numpy(d["rgb_sigma"]).clone()
