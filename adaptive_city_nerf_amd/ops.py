@@ -952,7 +952,57 @@ def distortion_dense(weights: torch.Tensor, t_vals: torch.Tensor, ray_scale: Opt
     return loss, grad
 
 
-RESAMPLE_MAX_S, RESAMPLE_MAX_F = 1024, 1024   # acn_resample_pdf's row limits (its LDS: 16 KB per ray)
+SSIM_TILE_H = SSIM_TILE_W = 32   # ACN_SSIM_TILE: map pixels (forward) / image pixels (gradient) per workgroup
+SSIM_MAX_WIN = 11                # the fused path takes odd window sizes 3 .. 11
+_SSIM_WS = {}
+
+
+def _ssim_ws(device, nbytes: int) -> torch.Tensor:
+    """Workspace of acn_ssim_fwd per (device, stream), grown on demand; it carries no state between calls.  Under
+    stream capture every captured call gets one of its own, as in _mse_ws."""
+    if torch.cuda.is_current_stream_capturing():
+        return _lib.capture_keepalive(torch.empty(nbytes, dtype=torch.uint8, device=device))
+    key = (device, int(torch.cuda.current_stream(device).cuda_stream))
+    ws = _SSIM_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _SSIM_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def ssim_fwd(x: torch.Tensor, y: torch.Tensor, *, channels_last: bool = False, win_size: int = 11,
+             win_sigma: float = 1.5, c1: float, c2: float, want_grad: bool = False):
+    """(ssim (N, C) fp32, d ssim[n, c] / d x in x's layout or None) of pytorch_msssim.ssim's definition
+    (acn_ssim_fwd): Gaussian window of ``win_size`` taps (odd, 3 .. 11) and ``win_sigma``, "valid"
+    filtering, stabilisers ``c1`` and ``c2``.  ``x`` and ``y`` are (N, C, H, W), or (N, H, W, C) with
+    ``channels_last`` (a rendered frame, read with no permute copy).  float64 arithmetic on the fp32 inputs, one fp32
+    rounding per output, bitwise reproducible; ssim(x, x) is exactly 1.  The gradient in ``y`` is
+    ``ssim_fwd(y, x, want_grad=True)``."""
+    if x.dim() != 4 or y.shape != x.shape:
+        raise AcnError(f"ssim_fwd: x and y must share one 4-D shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    N, C, H, W = (x.shape[0], x.shape[3], x.shape[1], x.shape[2]) if channels_last else x.shape
+    win = int(win_size)
+    if win % 2 != 1 or not 3 <= win <= SSIM_MAX_WIN:
+        raise AcnError(f"ssim_fwd: win_size must be odd and in 3..{SSIM_MAX_WIN}, got {win_size}")
+    if not float(win_sigma) > 0:
+        raise AcnError(f"ssim_fwd: win_sigma must be > 0, got {win_sigma}")
+    if C < 1 or H < win or W < win:
+        raise AcnError(f"ssim_fwd: needs C >= 1 and H, W >= win_size = {win}, got C = {C}, H = {H}, W = {W}")
+    require_hip(x, "ssim_fwd")
+    xv, yv = _f32(x), _f32(y)
+    if yv.device != xv.device:
+        raise AcnError("ssim_fwd: y must be on x's device")
+    out = torch.empty(N, C, device=xv.device, dtype=torch.float32)
+    grad = torch.empty_like(xv) if want_grad else None
+    if N == 0:
+        return out, grad
+    L = _lib.lib()
+    ws = _ssim_ws(xv.device, int(L.acn_ssim_workspace_bytes(N, C, H, W, int(want_grad))))
+    check(L.acn_ssim_fwd(ptr(xv), ptr(yv), N, C, H, W, int(bool(channels_last)), win, float(win_sigma), float(c1),
+                         float(c2), ptr(out), ptr(grad), ptr(ws), ws.numel(), stream_of(xv)), "acn_ssim_fwd")
+    return out, grad
+
+
+RESAMPLE_MAX_S, RESAMPLE_MAX_F = 1024, 1024  # acn_resample_pdf's row limits (its LDS: 16 KB per ray)
 
 
 def resample_pdf(weights: torch.Tensor, t_vals: torch.Tensor, n_fine: int, jitter: Optional[torch.Tensor] = None,

@@ -200,7 +200,9 @@ def render_image_sharded(model, *, H: int, W: int, fx: float, fy: float, cx: flo
     """Multi-GPU ``render_image`` (ray_rendering.py:577-627): every rank builds the frame's rays,
     renders its shard, and receives the whole frame.  Returns (rgb (H,W,3) clamped, depth (H*W,),
     acc (H*W,), psnr or None) -- psnr against ``gt_srgb`` (H,W,3) in ``metrics_space`` reduced
-    over ranks.  ``render_fn``/``rays`` override the HIP renderer and ray generator (tests)."""
+    over ranks.  ``render_fn``/``rays`` override the HIP renderer and ray generator (tests).  Every rank holds the
+    whole frame after the all-gather, so ``metrics.image_metrics(rgb, gt_srgb)`` (PSNR and SSIM) applies to the
+    result as it does to ``render_image``'s, with no further collective."""
     world, rank = _world_rank(group)
     if rays is None:
         from . import ops

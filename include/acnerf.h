@@ -636,6 +636,28 @@ int acn_distortion_dense(const float* weights, const float* t_vals, int64_t N, i
  * no-op. */
 int acn_resample_pdf(const float* weights, const float* t_vals, int64_t N, int S, const float* jitter, int F,
                      const float* rays, float* t_fine, float* t_merged, float* pts6, void* stream);
+/* Structural similarity (pytorch_msssim.ssim's definition) of the images x and y per image n and channel c, with its
+ * gradient in x (ssim.hip).  With the window g[i] = exp(-(i - win_size / 2)^2 / (2 win_sigma^2)) normalised to sum 1
+ * (built here in float64) and g* the separable "valid" correlation (no padding; maps of (H - win_size + 1) x
+ * (W - win_size + 1) pixels):
+ *   mu1 = g*x, mu2 = g*y, s1 = g*x^2 - mu1^2, s2 = g*y^2 - mu2^2, s12 = g*xy - mu1 mu2
+ *   cs = (2 s12 + c2) / (s1 + s2 + c2), map = (2 mu1 mu2 + c1) / (mu1^2 + mu2^2 + c1) * cs, ssim_nc[n, c] = mean(map)
+ * channels_last = 0: x and y are contiguous (N, C, H, W); 1: contiguous (N, H, W, C), read in place.
+ * Every product, both filter passes, the map, its mean and the gradient are float64 on the fp32 inputs; each element
+ * of ssim_nc (N*C) and grad_x is rounded to fp32 once.  The three second moments share one instruction sequence, so
+ * ssim(x, x) is exactly 1.  The map is summed per ACN_SSIM_TILE x ACN_SSIM_TILE tile into the workspace and the tiles
+ * of a plane are added in a fixed order by a second launch: no atomics, bitwise reproducible.
+ * grad_x, in x's layout, or NULL (the same ssim_nc bits): d ssim_nc[n, c] / d x[n, c, :, :], the transposed filter of
+ * the map's three partial derivatives (float64 planes in the workspace) contracted with x and y, one more launch.  The
+ * gradient in y is the same call with x and y swapped.
+ * win_size odd in 3..11, win_sigma > 0, H and W >= win_size, C >= 1, else ACN_ERR_ARG before any HIP call.  N == 0 is a
+ * no-op.  workspace: acn_ssim_workspace_bytes(N, C, H, W, grad_x != NULL) device bytes, 16-byte aligned, no
+ * initialisation needed (8 B per tile, and 24 B per map pixel with the gradient, sized for win_size = 3). */
+#define ACN_SSIM_TILE 32
+size_t acn_ssim_workspace_bytes(int64_t N, int C, int H, int W, int want_grad);
+int acn_ssim_fwd(const float* x, const float* y, int64_t N, int C, int H, int W, int channels_last, int win_size,
+                 double win_sigma, double c1, double c2, float* ssim_nc, float* grad_x, void* workspace,
+                 size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Episodic task routing (data.hip).  Replaces TaskDataset's region clip + micro-cell assignment
