@@ -14,9 +14,10 @@ from .encodings import FrequencyEncoder, HashGridEncoder, SHEncoder, components_
 from .meta_container import MetaContainer  # noqa: E402,F401
 from .meta_ngp import MetaNGP  # noqa: E402,F401
 from .metamodule import MetaBatchLinear, MetaLayerBlock, MetaLinear, MetaModule, MetaSequential  # noqa: E402,F401
-from .ray_rendering import (distortion_loss, render_expert_occ, render_image, render_normal_image, render_normals,  # noqa: E402,F401
-                            render_rays, render_rays_at, render_rays_hierarchical, render_rays_occ,
-                            render_rays_stratified, sample_pdf, stratified_t_vals, volume_render)
+from .ray_rendering import (distortion_loss, interlevel_loss, proposal_weights, render_expert_occ, render_image,  # noqa: E402,F401
+                            render_normal_image, render_normals, render_rays, render_rays_at,
+                            render_rays_hierarchical, render_rays_occ, render_rays_proposal, render_rays_stratified,
+                            sample_pdf, stratified_t_vals, volume_render)
 from . import nerfacc  # noqa: E402,F401
 from .nerfacc import OccGridEstimator  # noqa: E402,F401
 from .ray_sampling import clamp_rays_near_far, get_ray_directions, get_rays, pack_rays, unpack_rays  # noqa: E402,F401

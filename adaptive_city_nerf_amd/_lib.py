@@ -175,6 +175,8 @@ SIGNATURES = {
     "acn_distortion_dense": ([vp, vp, i64, i32, vp, vp, vp, vp], C.c_int),
     # resample.hip
     "acn_resample_pdf": ([vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp], C.c_int),
+    # interlevel.hip
+    "acn_interlevel_loss": ([vp, vp, i32, vp, vp, i32, i64, vp, C.c_double, vp, vp, vp], C.c_int),
     # ssim.hip
     "acn_ssim_workspace_bytes": ([i64, i32, i32, i32, i32], C.c_size_t),
     "acn_ssim_fwd": ([vp, vp, i64, i32, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, sz, vp],

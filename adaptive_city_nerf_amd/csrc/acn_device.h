@@ -61,6 +61,26 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// number of leading elements of the ascending a[0..n) for which pred holds (pred true on a prefix): `steps` >=
+// floor(log2 n) + 1 halvings.  a[] is read at indices < n only (the searches of resample.hip and interlevel.hip).
+template <typename T, typename Pred>
+__device__ __forceinline__ int prefix_count(const T* a, int n, int steps, Pred pred) {
+    int lo = 0, len = n;
+    for (int it = 0; it < steps; ++it) {
+        const int half = len >> 1;
+        const int mid = lo + half;
+        if (len > 0) {
+            if (pred(a[mid])) {
+                lo = mid + 1;
+                len -= half + 1;
+            } else {
+                len = half;
+            }
+        }
+    }
+    return lo;
+}
+
 // compute_mse_loss in color_space "linear" (nerfs/losses.py:10-32, color_space.py:13-19, 22-66): pred.clamp(0,1)
 // against gt.clamp(0,1) -> srgb_to_linear -> clamp(0,1); float scalars and powf as the torch ops (loss.hip and
 // the fused training compositing in render.hip)

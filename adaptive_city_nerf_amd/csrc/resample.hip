@@ -40,25 +40,7 @@ struct ResampleArgs {
     int32_t u_off;           // float offset of the CDF / merged region in a wave's LDS (even: the doubles are aligned)
 };
 
-// number of leading elements of the ascending a[0..n) for which pred holds (pred true on a prefix): `steps` >=
-// floor(log2 n) + 1 halvings.  a[] is read at indices < n only.
-template <typename T, typename Pred>
-__device__ __forceinline__ int prefix_count(const T* a, int n, int steps, Pred pred) {
-    int lo = 0, len = n;
-    for (int it = 0; it < steps; ++it) {
-        const int half = len >> 1;
-        const int mid = lo + half;
-        if (len > 0) {
-            if (pred(a[mid])) {
-                lo = mid + 1;
-                len -= half + 1;
-            } else {
-                len = half;
-            }
-        }
-    }
-    return lo;
-}
+using acn::prefix_count;   // acn_device.h (shared with interlevel.hip)
 
 __global__ void __launch_bounds__(kWaves * 64) resample_pdf_kernel(ResampleArgs a) {
     extern __shared__ double lds_raw[];   // double: 8-byte alignment of the base

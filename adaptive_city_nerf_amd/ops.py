@@ -1046,6 +1046,42 @@ def resample_pdf(weights: torch.Tensor, t_vals: torch.Tensor, n_fine: int, jitte
     return t_fine, t_merged, pts6
 
 
+INTERLEVEL_MAX_S, INTERLEVEL_MAX_P = 1024, 1024  # acn_interlevel_loss's row limits (its LDS: 12 (S + P + 2) B per ray)
+
+
+def interlevel_loss(t_fine: torch.Tensor, w_fine: torch.Tensor, t_prop: torch.Tensor, w_prop: torch.Tensor,
+                    ray_scale: Optional[torch.Tensor] = None, eps: float = 2.0 ** -23, want_grad: bool = True):
+    """(loss (N,), d loss / d w_prop (N, P) or None) of the mip-NeRF 360 interlevel ("proposal") loss
+    (acn_interlevel_loss): with the edges of a row of depths E(t) = [t_0 .. t_{S-1},
+    t_{S-1} + (t_{S-1} - t_{S-2})], a = E(t_fine) and p = E(t_prop),
+    bound_i = the sum of w_prop over the proposal intervals k with p_{k+1} > a_i and p_k < a_{i+1},
+    loss = sum_i max(0, w_fine_i - bound_i)^2 / (w_fine_i + eps), times ``ray_scale`` (N,) when given.  The fine
+    weights and all depths are constants.  One launch; float64 arithmetic, one fp32 rounding per output; bitwise
+    reproducible.  A ray whose scale is exactly 0 gets zeros and its depths are not read.  2 <= S, P <= 1024."""
+    if (t_fine.dim() != 2 or w_fine.shape != t_fine.shape or t_prop.dim() != 2 or w_prop.shape != t_prop.shape
+            or t_prop.shape[0] != t_fine.shape[0]):
+        raise AcnError(f"interlevel_loss: t_fine and w_fine must both be (N, S), t_prop and w_prop both (N, P), got "
+                       f"{tuple(t_fine.shape)}, {tuple(w_fine.shape)}, {tuple(t_prop.shape)} and "
+                       f"{tuple(w_prop.shape)}")
+    N, S = t_fine.shape
+    P = t_prop.shape[1]
+    if not (2 <= S <= INTERLEVEL_MAX_S and 2 <= P <= INTERLEVEL_MAX_P):
+        raise AcnError(f"interlevel_loss: needs 2 <= S <= {INTERLEVEL_MAX_S} fine and 2 <= P <= {INTERLEVEL_MAX_P} "
+                       f"proposal samples, got {S} and {P}")
+    if not float(eps) > 0:
+        raise AcnError(f"interlevel_loss: eps must be > 0, got {eps}")
+    require_hip(w_prop, "interlevel_loss")
+    wp, tp, tf, wf = _f32(w_prop), _f32(t_prop), _f32(t_fine), _f32(w_fine)
+    if not (tp.device == tf.device == wf.device == wp.device):
+        raise AcnError("interlevel_loss: the four arrays must be on one device")
+    rs = _ray_scale_arg(ray_scale, N, wp.device, "interlevel_loss")
+    loss = torch.empty(N, device=wp.device, dtype=torch.float32)
+    grad = torch.empty(N, P, device=wp.device, dtype=torch.float32) if want_grad else None
+    check(_lib.lib().acn_interlevel_loss(ptr(tf), ptr(wf), int(S), ptr(tp), ptr(wp), int(P), N, ptr(rs), float(eps),
+                                         ptr(loss), ptr(grad), stream_of(wp)), "acn_interlevel_loss")
+    return loss, grad
+
+
 def sample_stratified(rays: torch.Tensor, S: int, jitter: Optional[torch.Tensor], aabb_min, aabb_extent,
                       eps: float):
     """Training-path sampler (acn_sample_stratified): t_vals (N,S), x01 (N*S,3) in the expert's unit box

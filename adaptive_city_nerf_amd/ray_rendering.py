@@ -855,6 +855,199 @@ def render_rays_hierarchical(model, rays: Tensor, ray_samples: int, n_importance
     return out + (t_merged,) if return_t_vals else out
 
 
+# ============================== Proposal-guided rendering (mip-NeRF 360) ===============================
+FUSED_INTERLEVEL = True   # interlevel_loss on acn_interlevel_loss; tests switch it off to take the
+                          # torch chain
+
+
+def _edges64(t: Tensor) -> Tensor:
+    """(N, S + 1) float64 interval edges of (N, S >= 2) depths: e_i = t_i, e_S = t_{S-1} + (t_{S-1} - t_{S-2})."""
+    t = t.double()
+    return torch.cat([t, t[:, -1:] + (t[:, -1:] - t[:, -2:-1])], dim=1)
+
+
+def _interlevel_torch(t_vals: Tensor, weights: Tensor, t_prop: Tensor, w_prop: Tensor,
+                      ray_scale: Optional[Tensor] = None, eps: float = 2.0 ** -23) -> Tensor:
+    """(N,) interlevel loss as torch ops: acn_interlevel_loss's O(S + P) form with float64 scans and searches (CPU
+    tensors, other dtypes than fp32, rows beyond the kernel's limits, and inside second_order(): differentiable any
+    number of times in ``w_prop``).  A ray whose scale is 0 gets an exact 0 whatever its depths are."""
+    t, w, tp = t_vals.detach(), weights.detach().double(), t_prop.detach()
+    wp = w_prop.double()
+    if ray_scale is not None:
+        live = (ray_scale.detach() != 0).unsqueeze(1)
+        t, tp = torch.where(live, t, torch.zeros_like(t)), torch.where(live, tp, torch.zeros_like(tp))
+        w, wp = torch.where(live, w, torch.zeros_like(w)), torch.where(live, wp, torch.zeros_like(wp))
+    P = tp.shape[1]
+    a, p = _edges64(t), _edges64(tp).contiguous()
+    # proposal intervals [lo, hi) overlapped by fine interval i: lo the largest j with p_j <= a_i (0 if none), hi the
+    # smallest j with p_j >= a_{i+1} (P if none), raised to lo
+    lo = (torch.searchsorted(p, a[:, :-1].contiguous(), right=True) - 1).clamp_min(0)
+    hi = torch.maximum(torch.searchsorted(p, a[:, 1:].contiguous(), right=False).clamp_max(P), lo)
+    c = torch.cat([wp.new_zeros(wp.shape[0], 1), torch.cumsum(wp, dim=1)], dim=1)
+    # a range of one interval takes its weight itself, not a difference of sums (equal histograms give exactly 0)
+    bound = torch.where(hi == lo + 1, torch.gather(wp, 1, lo.clamp_max(P - 1)),
+                        torch.gather(c, 1, hi) - torch.gather(c, 1, lo))
+    x = (w - bound).clamp_min(0.0)
+    loss = (x * x / (w + float(eps))).sum(1)
+    if ray_scale is not None:
+        loss = torch.where(live.squeeze(1), loss * ray_scale.detach().double(), torch.zeros_like(loss))
+    return loss.to(w_prop.dtype)
+
+
+class _InterlevelFn(torch.autograd.Function):
+    """One HIP launch (acn_interlevel_loss) that returns the per-ray loss and keeps d loss / d w_prop for the
+    backward, which is g_loss[ray] * grad (the shape of nerfacc._DistortionFn)."""
+
+    @staticmethod
+    def forward(ctx, w_prop, t_vals, weights, t_prop, ray_scale, eps, want_grad):
+        loss, grad = ops.interlevel_loss(t_vals, weights, t_prop, w_prop, ray_scale, eps=eps, want_grad=want_grad)
+        ctx.set_materialize_grads(False)
+        if want_grad:
+            ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        if g_loss is None or not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        return (g_loss.unsqueeze(1) * ctx.saved_tensors[0],) + (None,) * 6
+
+
+def _interlevel_fused(t_vals: Tensor, weights: Tensor, t_prop: Tensor, w_prop: Tensor) -> bool:
+    return (FUSED_INTERLEVEL and not _second_order()
+            and all(x.is_cuda and x.dtype == torch.float32 for x in (t_vals, weights, t_prop, w_prop))
+            and t_vals.shape[1] <= ops.INTERLEVEL_MAX_S and t_prop.shape[1] <= ops.INTERLEVEL_MAX_P)
+
+
+def interlevel_loss(t_vals: Tensor, weights: Tensor, t_prop: Tensor, w_prop: Tensor, rays: Optional[Tensor] = None,
+                    reduction: str = "mean", eps: float = 2.0 ** -23) -> Tensor:
+    """The mip-NeRF 360 interlevel ("proposal") loss: the proposal's weight histogram along a ray must upper-bound
+    the main model's.  ``t_vals`` / ``weights`` (N, S >= 2) are the fine render's depths and weights, ``t_prop`` /
+    ``w_prop`` (N, P >= 2) the proposal's (``proposal_weights``).  A row of depths t owns the intervals between the
+    edges [t_0 .. t_{S-1}, t_{S-1} + (t_{S-1} - t_{S-2})] (the compositing's own intervals, without volume_render's
+    1e-4 clamp); with bound_i the sum of ``w_prop`` over the proposal intervals that overlap fine interval i,
+
+        loss = sum_i max(0, w_i - bound_i)^2 / (w_i + eps)
+
+    per ray.  ``weights`` and all depths are detached: the fine weights are the target, the only gradient is in
+    ``w_prop``.  On ties this is deliberately the tight bound: two intervals that only share an edge do not overlap, so
+    a fine interval that ends exactly on a proposal edge does not count the next proposal interval (multinerf's
+    ``lossfun_outer`` counts it; parity with multinerf is unpinned, the package is not available here).
+    ``rays`` (N, >=8) zeroes the rays without far > near (an invalid ray with NaN bounds contributes an exact 0).
+    ``reduction``: none (N,) | mean | sum.  HIP fp32 tensors with S, P <= 1024 outside second_order() take one
+    launch for loss and gradient (acn_interlevel_loss: float64 arithmetic, one fp32 rounding per output); everything
+    else the same definition as float64 torch ops, differentiable any number of times in ``w_prop``."""
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError(f"interlevel_loss: reduction must be none, mean or sum, got {reduction!r}")
+    if (t_vals.dim() != 2 or t_vals.shape[1] < 2 or weights.shape != t_vals.shape or t_prop.dim() != 2
+            or t_prop.shape[1] < 2 or w_prop.shape != t_prop.shape or t_prop.shape[0] != t_vals.shape[0]):
+        raise ops.AcnError(f"interlevel_loss: t_vals and weights must both be (N, S >= 2), t_prop and w_prop both "
+                           f"(N, P >= 2), got {tuple(t_vals.shape)}, {tuple(weights.shape)}, {tuple(t_prop.shape)} "
+                           f"and {tuple(w_prop.shape)}")
+    if not float(eps) > 0:
+        raise ops.AcnError(f"interlevel_loss: eps must be > 0, got {eps}")
+    dev = w_prop.device
+    t_vals, weights, t_prop = t_vals.detach().to(dev), weights.detach().to(dev), t_prop.detach().to(dev)
+    scale = None
+    if rays is not None:
+        if rays.dim() != 2 or rays.shape[0] != w_prop.shape[0] or rays.shape[1] < 8:
+            raise ops.AcnError(f"interlevel_loss: rays must be ({w_prop.shape[0]}, >=8), got {tuple(rays.shape)}")
+        near, far = rays.detach()[:, 6].to(dev), rays.detach()[:, 7].to(dev)
+        scale = torch.where(far > near, torch.ones_like(far), torch.zeros_like(far))
+    if _interlevel_fused(t_vals, weights, t_prop, w_prop):
+        loss = _InterlevelFn.apply(w_prop, t_vals, weights, t_prop, scale, float(eps),
+                                   torch.is_grad_enabled() and w_prop.requires_grad)
+    else:
+        loss = _interlevel_torch(t_vals, weights, t_prop, w_prop, ray_scale=scale, eps=eps)
+    if reduction == "none":
+        return loss
+    return loss.mean() if reduction == "mean" else loss.sum()
+
+
+def _proposal_weights_torch(sigma: Tensor, t: Tensor, sigma_scale) -> Tensor:
+    """w = T alpha, alpha_i = 1 - exp(-sigma_i s d_i), T_i = exp(-sum_{j<i} sigma_j s d_j), d the widths of the rows'
+    own intervals (_edges64), in float64 and rounded to sigma's dtype."""
+    e = _edges64(t)
+    tau = sigma.double() * sigma_scale * (e[:, 1:] - e[:, :-1])
+    w = torch.exp(-(torch.cumsum(tau, dim=1) - tau)) * (1.0 - torch.exp(-tau))
+    return w.to(sigma.dtype)
+
+
+def proposal_weights(proposal, rays: Tensor, n_proposal: int, params=None, sigma_scale=1.0,
+                     jitter_u: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(t_prop (N, P), w_prop (N, P)): the compositing weights of a density-only proposal field along the rays, at
+    ``n_proposal`` stratified depths (stratified_t_vals, jittered iff ``proposal.training``, with ``jitter_u`` (N, P)
+    as the uniforms).  ``proposal`` is any module with ``density(x (..., 3), params=None) -> (..., 1)``; a small
+    MetaNGP of a few coarse hash levels is the intended one (its no-grad density is the fused field kernel, with grad
+    it is the HIP hash grid plus the sigma branch).  Sample i owns [e_i, e_{i+1}], e the row's depths and one edge
+    synthesised past the last (interlevel_loss's intervals); alpha_i = 1 - exp(-sigma_i sigma_scale d_i), T the
+    exclusive product of 1 - alpha, w = T alpha.  On HIP fp32 that is nerfacc.render_weight_from_density on the packed
+    view (P samples per ray; forward and backward kernels), elsewhere the formula as float64 torch ops.  Differentiable
+    in the proposal's parameters (and fast weights), never in the depths or the rays."""
+    P = int(n_proposal)
+    if P < 2:
+        raise ops.AcnError(f"proposal_weights: n_proposal must be >= 2, got {n_proposal}")
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise ops.AcnError(f"proposal_weights: rays must be (N, >=8), got {tuple(rays.shape)}")
+    r = rays.detach()
+    N = r.shape[0]
+    t = stratified_t_vals(r[:, 6], r[:, 7], P, randomized=bool(proposal.training), u=jitter_u)
+    pts = r[:, None, :3] + r[:, None, 3:6] * t.unsqueeze(-1)
+    sigma = proposal.density(pts.reshape(-1, 3), params=params).reshape(N, P)
+    if sigma.is_cuda and sigma.dtype == torch.float32 and t.dtype == torch.float32 and not _second_order():
+        t_end = torch.cat([t[:, 1:], t[:, -1:] + (t[:, -1:] - t[:, -2:-1])], dim=1)
+        starts = torch.arange(N, dtype=torch.long, device=sigma.device) * P
+        info = torch.stack([starts, torch.full_like(starts, P)], dim=-1)
+        w, _, _ = nerfacc.render_weight_from_density(t.reshape(-1), t_end.reshape(-1),
+                                                     (sigma * sigma_scale).reshape(-1), packed_info=info)
+        return t, w.view(N, P)
+    return t, _proposal_weights_torch(sigma, t, sigma_scale)
+
+
+def render_rays_proposal(model, proposal, rays: Tensor, n_proposal: int, n_fine: int, params=None,
+                         proposal_params=None, active_module: Optional[int] = None, bg_color_default: str = "white",
+                         sigma_scale=1.0, chunk: int = 1_000_000, jitter_u: Optional[Tensor] = None,
+                         jitter_fine: Optional[Tensor] = None, return_proposal: bool = False,
+                         return_t_vals: bool = False, **kwargs):
+    """Proposal-guided stratified renderer (mip-NeRF 360): the density-only ``proposal`` field is evaluated at
+    ``n_proposal`` stratified depths (proposal_weights), ``n_fine`` depths per ray are drawn where its weights are
+    (sample_pdf on the detached weights), and ``model`` is evaluated at those ``n_fine`` depths only (render_rays_at)
+    -- not at the merged depths: evaluating the main model only where the proposal puts mass is the point.  Returns
+    the fine pass: rgb (N,3), depth (N,), weights (N, n_fine), acc (N,).
+
+    ``return_proposal`` appends (t_prop, w_prop) as one tuple, ``w_prop`` differentiable in the proposal's parameters
+    (``interlevel_loss(t_fine, weights, t_prop, w_prop, rays)`` trains it); ``return_t_vals`` appends the (N, n_fine)
+    fine depths last.  The resampling carries no gradient: the image loss never reaches the proposal.  The fine
+    quantiles are jittered by ``jitter_fine`` (N, n_fine) or torch.rand when ``model.training`` and are the bin
+    centres otherwise; ``jitter_u`` (N, n_proposal) goes to the proposal's depths.  ``params`` are the model's fast
+    weights, ``proposal_params`` the proposal's.  One proposal covers the whole scene box of a container.  In eval mode
+    without gradients this is the proposal's fused field launch, the weights, the resampling, the ray order and the
+    fused render at depths."""
+    P, F = int(n_proposal), int(n_fine)
+    if P < 3:
+        raise ops.AcnError(f"render_rays_proposal: the resampling needs n_proposal >= 3, got {n_proposal}")
+    if F < 2:
+        raise ops.AcnError(f"render_rays_proposal: the render needs n_fine >= 2, got {n_fine}")
+    kwargs.pop("_want_weights", None)   # the caller of the interlevel loss needs the weights whatever render_image keeps
+    early_stop_tau = float(kwargs.pop("early_stop_tau", 0.0))
+    if kwargs:
+        raise TypeError(f"render_rays_proposal: unexpected arguments {sorted(kwargs)}")
+    N = rays.shape[0]
+    t_prop, w_prop = proposal_weights(proposal, rays, P, params=proposal_params, sigma_scale=sigma_scale,
+                                      jitter_u=jitter_u)
+    jitter = None
+    if model.training:
+        jitter = jitter_fine if jitter_fine is not None else torch.rand(N, F, device=rays.device)
+    t_fine = sample_pdf(t_prop, w_prop.detach(), F, jitter)
+    out = render_rays_at(model, rays, t_fine, params=params, active_module=active_module,
+                         bg_color_default=bg_color_default, chunk=chunk, sigma_scale=sigma_scale,
+                         early_stop_tau=early_stop_tau)
+    if return_proposal:
+        out += ((t_prop, w_prop),)
+    return out + (t_fine,) if return_t_vals else out
+
+
 _STRATIFIED_POSITIONALS = ("ray_samples", "params", "active_module", "bg_color_default", "chunk", "sigma_scale",
                            "return_t_vals")
 
@@ -862,8 +1055,22 @@ _STRATIFIED_POSITIONALS = ("ray_samples", "params", "active_module", "bg_color_d
 def render_rays(model, rays, *args, **kwargs):
     """Entry point (:564-574): occupancy renderer once the model's grids are ready, else stratified.
     ``n_importance`` = K > 0 (an extension) renders coarse to fine (render_rays_hierarchical) with K further depths
-    per ray; it is an error once the occupancy renderer is active, which concentrates its samples by marching."""
+    per ray; it is an error once the occupancy renderer is active, which concentrates its samples by marching.
+    ``proposal`` (an extension, with ``n_importance`` = F > 0) renders proposal-guided instead
+    (render_rays_proposal): the proposal field at ``ray_samples`` depths, the model at F resampled depths."""
     n_importance = int(kwargs.pop("n_importance", 0) or 0)
+    proposal = kwargs.pop("proposal", None)
+    if proposal is not None:
+        if n_importance <= 0:
+            raise ops.AcnError("render_rays(proposal=...): the proposal-guided render needs n_importance > 0, the "
+                               "number of depths the model is evaluated at")
+        if getattr(model, "use_occ", False) and model.occ_ready:
+            raise ops.AcnError("render_rays(proposal=...): the occupancy renderer concentrates its samples by "
+                               "marching; a proposal goes with the stratified renderer")
+        if len(args) > len(_STRATIFIED_POSITIONALS):
+            raise TypeError("render_rays: too many positional arguments")
+        kwargs.update(zip(_STRATIFIED_POSITIONALS, args))   # render_rays_stratified's positional order
+        return render_rays_proposal(model, proposal, rays, kwargs.pop("ray_samples"), n_importance, **kwargs)
     if n_importance > 0:
         if getattr(model, "use_occ", False) and model.occ_ready:
             raise ops.AcnError("render_rays(n_importance > 0): the occupancy renderer concentrates its samples by "

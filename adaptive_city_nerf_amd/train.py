@@ -28,7 +28,7 @@ from . import ops
 from ._lib import graph_capture
 from .color_space import color_space_transformer
 from .optim import FusedAdam
-from .ray_rendering import distortion_loss, render_rays
+from .ray_rendering import distortion_loss, interlevel_loss, render_rays
 
 
 class _MSELinearFn(torch.autograd.Function):
@@ -67,12 +67,30 @@ def compute_mse_loss(P, model, data, params=None, active_module=None, reduction:
 
 
 def compute_loss(P, model, data, params=None, active_module=None, reduction: str = "mean",
-                 distortion_weight: float = 0.0, **render_kwargs):
+                 distortion_weight: float = 0.0, proposal=None, interlevel_weight: float = 1.0, **render_kwargs):
     """compute_mse_loss plus ``distortion_weight`` times the mean distortion loss of the render's weights
     (ray_rendering.distortion_loss, every ray normalised to unit length): the mip-NeRF 360 regulariser against
     semi-transparent fog and floaters between the camera and the surface.  With weight 0 it is compute_mse_loss, from
     the same calls.  The regulariser needs the stratified renderer's (N,S) weights and t values: with the occupancy
-    renderer active, render_rays raises (take nerfacc.distortion of the packed samples instead)."""
+    renderer active, render_rays raises (take nerfacc.distortion of the packed samples instead).
+
+    ``proposal`` (a density-only field, ray_rendering.proposal_weights) renders proposal-guided
+    (render_rays_proposal; ``n_importance`` in the render kwargs is the number of depths the model is evaluated at,
+    ``P.ray_samples`` the proposal's) and adds ``interlevel_weight`` times the mean interlevel loss, which trains the
+    proposal and carries no gradient to the model; the image loss carries none to the proposal."""
+    if proposal is not None:
+        if not render_kwargs.get("n_importance"):
+            raise ValueError("compute_loss: a proposal needs n_importance > 0 in the render arguments (the number of "
+                             "depths the model is evaluated at)")
+        rays = data["rays"]
+        pred_rgb, _, weights, _, (t_prop, w_prop), t_vals = render_rays(
+            model, rays, ray_samples=P.ray_samples, params=params, active_module=active_module, chunk=P.chunk_points,
+            proposal=proposal, return_proposal=True, return_t_vals=True, **render_kwargs)
+        loss = mse_color_loss(pred_rgb, data["rgbs"], P.color_space, reduction)
+        if distortion_weight:
+            loss = loss + float(distortion_weight) * distortion_loss(weights, t_vals, rays=rays, reduction="mean")
+        return loss + float(interlevel_weight) * interlevel_loss(t_vals, weights, t_prop, w_prop, rays=rays,
+                                                                 reduction="mean")
     if not distortion_weight:
         return compute_mse_loss(P, model, data, params=params, active_module=active_module, reduction=reduction,
                                 **render_kwargs)
@@ -87,11 +105,13 @@ def compute_loss(P, model, data, params=None, active_module=None, reduction: str
 
 def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Optional[float] = 1.0,
                group=None, shared: Optional[list] = None, grad_scaler=None, distortion_weight: float = 0.0,
-               **render_kwargs) -> torch.Tensor:
+               proposal=None, interlevel_weight: float = 1.0, **render_kwargs) -> torch.Tensor:
     """One optimizer update of runtime_adapt (runtime_adapt.py:288-313).  Returns the loss (device).
     ``distortion_weight`` > 0 adds that multiple of the mean distortion loss (compute_loss) to the MSE.
     ``n_importance`` = K > 0 (through ``render_kwargs``, with ``jitter_fine``) trains on the coarse-to-fine render
     (render_rays_hierarchical): the loss is taken on the fine pass.
+    ``proposal`` (with ``n_importance``) trains on the proposal-guided render and adds ``interlevel_weight`` times the
+    interlevel loss (compute_loss), which trains the proposal: its parameters must be in ``optimizer``.
 
     ``group`` (expert parallel): ``rays`` / ``rgbs`` are this rank's shard of the global batch, the
     container's experts are distributed over the group (expert_parallel.adapt_step_expert_parallel);
@@ -105,6 +125,13 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
     if group is not None and render_kwargs.get("n_importance"):
         raise ValueError("adapt_step: the expert-parallel step renders one stratified pass (n_importance must be 0 "
                          "with a group)")
+    if group is not None and proposal is not None:
+        raise ValueError("adapt_step: the expert-parallel step renders one stratified pass (no proposal with a group)")
+    if proposal is not None:
+        held = {id(p) for g in optimizer.param_groups for p in g["params"]}
+        if not any(id(p) in held for p in proposal.parameters()):
+            raise ValueError("adapt_step: none of the proposal's parameters is in the optimizer; the interlevel loss "
+                             "would train nothing")
     if group is not None and torch.distributed.is_initialized() and torch.distributed.get_world_size(group) > 1:
         from .expert_parallel import HipBackend, adapt_step_expert_parallel
         if active_module is not None:
@@ -117,7 +144,10 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
                                           u=render_kwargs.get("jitter_u"))
     optimizer.zero_grad()
     loss = compute_loss(P, model=base, data={"rays": rays, "rgbs": rgbs}, params=None, active_module=active_module,
-                        reduction="mean", distortion_weight=distortion_weight, **render_kwargs)
+                        reduction="mean", distortion_weight=distortion_weight, proposal=proposal,
+                        interlevel_weight=interlevel_weight, **render_kwargs)
+    # without FusedAdam the clip norm is taken over the base's and the proposal's parameters together
+    clipped = base.parameters() if proposal is None else list(base.parameters()) + list(proposal.parameters())
     if ops.TRAIN_MLP_PRECISION == "amp":
         scaler = grad_scaler if grad_scaler is not None else torch.amp.GradScaler("cuda")
         scaler.scale(loss).backward()
@@ -126,7 +156,7 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
             scaler.step(optimizer, max_norm=grad_clip)
         else:
             if grad_clip is not None:
-                torch.nn.utils.clip_grad_norm_(base.parameters(), grad_clip)
+                torch.nn.utils.clip_grad_norm_(clipped, grad_clip)
             scaler.step(optimizer)
         scaler.update()
         return loss.detach()
@@ -135,7 +165,7 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
         optimizer.step(max_norm=grad_clip)  # clip_grad_norm_ folded into the fused step
     else:
         if grad_clip is not None:
-            torch.nn.utils.clip_grad_norm_(base.parameters(), grad_clip)
+            torch.nn.utils.clip_grad_norm_(clipped, grad_clip)
         optimizer.step()
     return loss.detach()
 
@@ -149,11 +179,15 @@ class GraphedAdaptStep:
     (``active_module``, the C5 / meta-training placement) or a bare MetaNGP -- the routed container's
     per-expert index selection is data-dependent.  Expert-parallel groups are not captured (use
     adapt_step).  ``distortion_weight`` as in adapt_step: the distortion launch and its backward multiply make no
-    host synchronisation, so they are captured with the rest."""
+    host synchronisation, so they are captured with the rest.  The proposal-guided step is not captured (use
+    adapt_step)."""
 
     def __init__(self, P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Optional[float] = 1.0,
-                 warmup: int = 2, max_steps: int = 1 << 16, distortion_weight: float = 0.0, **render_kwargs):
+                 warmup: int = 2, max_steps: int = 1 << 16, distortion_weight: float = 0.0, proposal=None,
+                 **render_kwargs):
         from .meta_container import MetaContainer
+        if proposal is not None:
+            raise ValueError("GraphedAdaptStep: the proposal-guided render is not captured; use adapt_step")
         if render_kwargs.get("n_importance"):
             raise ValueError("GraphedAdaptStep: the hierarchical render (n_importance > 0) is not captured; use "
                              "adapt_step")
@@ -242,7 +276,8 @@ FAST_RUNTIME_ADAPT = os.environ.get("ACN_FAST_ADAPT", "1") != "0"
 
 def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional[int] = None,
                   active_module: Optional[int] = None, grad_clip: Optional[float] = 1.0,
-                  distortion_weight: float = 0.0) -> Dict[str, float]:
+                  distortion_weight: float = 0.0, proposal=None, interlevel_weight: float = 1.0,
+                  n_importance: int = 0) -> Dict[str, float]:
     """runtime_adapt.py:213-315: adapt in place; one pass over the loader (steps=None) or exactly
     ``steps`` updates cycling over it.
 
@@ -252,14 +287,24 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
     synchronisation; a smaller (ragged last) batch runs the same kernels eagerly.  The loss is read once,
     at the end (the reference reads it every step).  Other configurations take the eager adapt_step, and so does
     every configuration with ``distortion_weight`` > 0 (adapt_step; the RoutedAdaptStep's fused composite-plus-MSE
-    kernel has no regulariser, so none is built)."""
+    kernel has no regulariser, so none is built), and every configuration with ``n_importance`` > 0 or a
+    ``proposal``: the proposal-guided step evaluates the model at ``n_importance`` depths and adds
+    ``interlevel_weight`` times the interlevel loss; the proposal, whose parameters must be in ``optimizer``, is put in
+    training mode too."""
     device = next(model.parameters()).device
     model.train()
+    if proposal is not None:
+        proposal.train()
     # the reference clips base.parameters(); parameters outside base get no gradient from the loss
     # (zero_grad sets them to None), so FusedAdam's norm over gradient-carrying tensors is the same
     base = model.submodules[active_module] if active_module is not None else model
     last_loss, step_count = None, 0
-    fast = [None, active_module is None and not distortion_weight]   # [RoutedAdaptStep, still worth trying]
+    extra = {}
+    if proposal is not None:
+        extra.update(proposal=proposal, interlevel_weight=interlevel_weight)
+    if n_importance:
+        extra["n_importance"] = int(n_importance)
+    fast = [None, active_module is None and not distortion_weight and not extra]   # [RoutedAdaptStep, worth trying]
     # use_amp: a fresh GradScaler per call (runtime_adapt.py:237); the cached RoutedAdaptStep's scaler restarts too
     amp = ops.TRAIN_MLP_PRECISION == "amp"
     scaler = torch.amp.GradScaler("cuda") if amp else None
@@ -278,7 +323,7 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
             last_loss = fast[0](rays, rgbs)
         else:
             last_loss = adapt_step(P, base, rays, rgbs, optimizer, active_module=active_module, grad_clip=grad_clip,
-                                   grad_scaler=scaler, distortion_weight=distortion_weight)
+                                   grad_scaler=scaler, distortion_weight=distortion_weight, **extra)
         step_count += 1
 
     if steps is None:

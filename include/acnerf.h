@@ -636,6 +636,28 @@ int acn_distortion_dense(const float* weights, const float* t_vals, int64_t N, i
  * no-op. */
 int acn_resample_pdf(const float* weights, const float* t_vals, int64_t N, int S, const float* jitter, int F,
                      const float* rays, float* t_fine, float* t_merged, float* pts6, void* stream);
+/* The interlevel ("proposal") loss of the mip-NeRF 360 recipe and its gradient in the proposal's weights, in one launch
+ * (interlevel.hip): the proposal's weight histogram along a ray must upper-bound the main model's.  Per ray, in float64
+ * on the fp32 inputs (depths non-decreasing, weights >= 0), with the edges E(t)_i = t_i (i < S) and
+ * E(t)_S = t_{S-1} + (t_{S-1} - t_{S-2}) -- the compositing's own intervals without the 1e-4 clamp -- a = E(t_fine),
+ * p = E(t_prop):
+ *   O(i,k)  = (p_{k+1} > a_i) and (p_k < a_{i+1})           fine interval i overlaps proposal interval k
+ *   bound_i = sum_k O(i,k) w_prop_k,  x_i = max(0, w_fine_i - bound_i)
+ *   loss    = scale * sum_i x_i^2 / (w_fine_i + eps)
+ *   grad_w_prop_k = -scale * sum_i O(i,k) 2 x_i / (w_fine_i + eps)
+ * w_fine and all depths are constants (the fine weights are the target).  On ties this is the tight bound: a fine
+ * interval that ends exactly on a proposal edge does not count the next proposal interval.  Evaluated in O(S + P): both
+ * edge rows are sorted, so the overlapped k (and i) are index ranges found by binary searches, and the sums are
+ * differences of the exclusive float64 prefix sums of w_prop and of 2 x / (w + eps) (a range of one proposal interval
+ * takes its weight itself: equal histograms give exactly 0).  loss (N) and each gradient element are rounded to fp32
+ * once.  One wave per ray, every binary search a fixed number of steps inside the ray's own arrays: a row that breaks
+ * the preconditions (NaN or unsorted depths) may hold garbage, but only its own row; no atomics, bitwise reproducible.
+ * ray_scale (N) or NULL: a ray whose scale is exactly 0.0f is skipped, zeros are written and its depths and weights are
+ * not read.  grad_w_prop (N, P) or NULL (loss only; the same loss bits).  2 <= S <= 1024 and 2 <= P <= 1024, else
+ * ACN_ERR_UNSUPPORTED before any HIP call.  N == 0 is a no-op. */
+int acn_interlevel_loss(const float* t_fine, const float* w_fine, int S, const float* t_prop, const float* w_prop,
+                        int P, int64_t N, const float* ray_scale, double eps, float* loss, float* grad_w_prop,
+                        void* stream);
 /* Structural similarity (pytorch_msssim.ssim's definition) of the images x and y per image n and channel c, with its
  * gradient in x (ssim.hip).  With the window g[i] = exp(-(i - win_size / 2)^2 / (2 win_sigma^2)) normalised to sum 1
  * (built here in float64) and g* the separable "valid" correlation (no padding; maps of (H - win_size + 1) x
