@@ -25,9 +25,11 @@
 #include "acn_device.h"
 #include "acn_internal.h"
 
-// This file is compiled twice into libacnerf.so: the default build (fp16x3 layer products) exports the
+// This file is compiled three times into libacnerf.so: the default build (fp16x3 layer products) exports the
 // acn_mlp_* entry points, a second object built with -DACN_TRAIN_F16X3=0 -DACN_MLP_SUFFIX=_exact exports
-// the exact-fp32 variants as acn_mlp_*_exact (a runtime precision switch: ops.set_train_mlp_precision).
+// the exact-fp32 variants as acn_mlp_*_exact, a third built with -DACN_TRAIN_AMP=1 -DACN_MLP_SUFFIX=_amp the
+// autocast(float16) arithmetic as acn_mlp_*_amp (a runtime precision switch: ops.set_train_mlp_precision).
+// ACN_MLP_SUFFIX, ACN_TRAIN_F16X3 and ACN_TRAIN_AMP are the file's only build parameters.
 #ifndef ACN_MLP_SUFFIX
 #define ACN_MLP_SUFFIX
 #endif
@@ -292,19 +294,9 @@ __device__ __forceinline__ f16x8 cat44(const f16x4& a, const f16x4& b) {
     return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-#ifndef ACN_MLP_KPIPE
-#define ACN_MLP_KPIPE 1   // fp16x3 fwd_layer / bwd_layer: the next k-step's A operands read ahead (0: at their k-step)
-#endif
-#ifndef ACN_MLP_BIASV
-#define ACN_MLP_BIASV 1   // fp16x3 fwd_layer epilogue: 16-B bias reads (0: one LDS read per element)
-#endif
-#ifndef ACN_MLP_ILV
-// fp16x3 layer products: the output tiles' MFMA chains interleaved per k-step.  Off: meta 61.73 -> 62.03 ms with
-// it (the producers of mlp_bwd_dw_pc_kernel 214 -> 217.5 us), C5 1.743 -> 1.728 ms
-#define ACN_MLP_ILV 0
-#endif
 // Y[to] (rows 32to..) = b + W . X  (W: hi / lo planes of 32*NT padded rows, ld = stride in halves,
-// ROWS = rows of the region; X: KT input tiles)
+// ROWS = rows of the region; X: KT input tiles).  The output tiles run one after the other, each on its own
+// MFMA chain (interleaving the tiles' chains per k-step measured slower).
 template <int NT, int KT, int ROWS>
 __device__ __forceinline__ void fwd_layer(const float* W, int ld, const float* b, const f32x16 (&X)[KT],
                                           f32x16 (&Y)[NT], int lane) {
@@ -334,37 +326,10 @@ __device__ __forceinline__ void fwd_layer(const float* W, int ld, const float* b
     split_tiles<KT>(X, k, bh, bl);
     const _Float16* Wh = reinterpret_cast<const _Float16*>(W);
     const _Float16* Wlo = Wh + ROWS * ld;
-#if ACN_MLP_ILV
-    // the NT output tiles' chains interleaved, k-step by k-step, with the k-step's A operands of every tile read
-    // first (each tile's own chain keeps its order: the same sums bit for bit); Y is the accumulator
-#pragma unroll
-    for (int to = 0; to < NT; ++to) Y[to] = 0.0f;
-#pragma unroll
-    for (int s = 0; s < 2 * KT; ++s) {
-        f16x8 ahi[NT], alo[NT];
-#pragma unroll
-        for (int to = 0; to < NT; ++to) {
-            const int c0 = (32 * to + i) * ld + 32 * (s >> 1) + 16 * (s & 1) + 4 * h;
-            ahi[to] = cat44(*reinterpret_cast<const f16x4*>(Wh + c0), *reinterpret_cast<const f16x4*>(Wh + c0 + 8));
-            alo[to] = cat44(*reinterpret_cast<const f16x4*>(Wlo + c0), *reinterpret_cast<const f16x4*>(Wlo + c0 + 8));
-        }
-#pragma unroll
-        for (int to = 0; to < NT; ++to) Y[to] = mfma_h(alo[to], bh[s], Y[to]);
-#pragma unroll
-        for (int to = 0; to < NT; ++to) Y[to] = mfma_h(ahi[to], bl[s], Y[to]);
-#pragma unroll
-        for (int to = 0; to < NT; ++to) Y[to] = mfma_h(ahi[to], bh[s], Y[to]);
-    }
-#pragma unroll
-    for (int to = 0; to < NT; ++to)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Y[to][r] = __builtin_fmaf(Y[to][r], usc, b[32 * to + rho(r, h)]);
-#else
 #pragma unroll
     for (int to = 0; to < NT; ++to) {
         const int ro = (32 * to + i) * ld;
         f32x16 acc = 0.0f;
-#if ACN_MLP_KPIPE
         // the next k-step's A operands are read while this k-step's MFMAs run (same chain, same order)
         auto lda = [&](int s, f16x8& ahi, f16x8& alo) {
             const int c0 = ro + 32 * (s >> 1) + 16 * (s & 1) + 4 * h;
@@ -383,40 +348,20 @@ __device__ __forceinline__ void fwd_layer(const float* W, int ld, const float* b
             ahi = nhi;
             alo = nlo;
         }
-#else
-#pragma unroll
-        for (int s = 0; s < 2 * KT; ++s) {
-            const int c0 = ro + 32 * (s >> 1) + 16 * (s & 1) + 4 * h;
-            const f16x8 ahi = cat44(*reinterpret_cast<const f16x4*>(Wh + c0), *reinterpret_cast<const f16x4*>(Wh + c0 + 8));
-            const f16x8 alo = cat44(*reinterpret_cast<const f16x4*>(Wlo + c0), *reinterpret_cast<const f16x4*>(Wlo + c0 + 8));
-            acc = mfma_h(alo, bh[s], acc);
-            acc = mfma_h(ahi, bl[s], acc);
-            acc = mfma_h(ahi, bh[s], acc);
-        }
-#endif
         // acc * 2^-k + b in one rounding (the scaling itself is exact); the bias rows rho(4q .. 4q + 3, h) are 4
         // consecutive floats, read as one 16-B vector each (the image's bias regions are 16-B aligned)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-#if ACN_MLP_BIASV
             typedef float f32x4b __attribute__((ext_vector_type(4)));
             const f32x4b bv = *reinterpret_cast<const f32x4b*>(b + 32 * to + 8 * q + 4 * h);
 #pragma unroll
             for (int e = 0; e < 4; ++e) Y[to][4 * q + e] = __builtin_fmaf(acc[4 * q + e], usc, bv[e]);
-#else
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                Y[to][4 * q + e] = __builtin_fmaf(acc[4 * q + e], usc, b[32 * to + rho(4 * q + e, h)]);
-#endif
         }
     }
 #endif
-#endif
 }
 
-#ifndef ACN_BWD_TR16
-#define ACN_BWD_TR16 1  // transposed weight reads of the backward layers on ds_read_b64_tr_b16 (0: ds_read_u16)
-#endif
+// the backward layers read W transposed on ds_read_b64_tr_b16
 typedef __fp16 hf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) hf16x4 lds_hf16x4;
 // ds_read_b64_tr_b16 (gfx950): per 16-lane group, lane 4q + p supplies the address of row q, columns 4p..4p+3
@@ -434,49 +379,34 @@ __device__ __forceinline__ f16x4 ds_read_tr16(const _Float16* p) {
 template <int NT, int KT, int NROW, int ROWS>
 __device__ __forceinline__ void bwd_layer(const float* W, int ld, const f32x16 (&dY)[KT], f32x16 (&dX)[NT],
                                           int lane) {
-    const int i = lane & 31, h = lane >> 5;
+    const int h = lane >> 5;
 #if ACN_TRAIN_AMP
+    (void)ROWS;
     f16x8 bh[2 * KT];
     cvt_tiles<KT>(dY, bh);
+    const _Float16* Wh = reinterpret_cast<const _Float16*>(W);
+    const int trow = 4 * h + ((lane >> 2) & 3), tcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti) {
+        f32x16 acc = 0.0f;
+#pragma unroll
+        for (int s = 0; s < 2 * KT; ++s) {
+            if (32 * (s >> 1) + 16 * (s & 1) >= NROW) continue;
+            const int o = (32 * (s >> 1) + 16 * (s & 1) + trow) * ld + 32 * ti + tcol;
+            const f16x8 ahi = cat44(ds_read_tr16(Wh + o), ds_read_tr16(Wh + o + 8 * ld));
+            acc = mfma_h(ahi, bh[s], acc);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dX[ti][r] = amp_r(acc[r]);
+    }
 #else
     const int k = tile_scale_exp<KT>(dY);
     const float usc = ldexpf(1.0f, -k);
     f16x8 bh[2 * KT], bl[2 * KT];
     split_tiles<KT>(dY, k, bh, bl);
-#endif
     const _Float16* Wh = reinterpret_cast<const _Float16*>(W);
     const _Float16* Wlo = Wh + ROWS * ld;
-#if ACN_BWD_TR16
     const int trow = 4 * h + ((lane >> 2) & 3), tcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-#endif
-#if ACN_MLP_ILV && ACN_BWD_TR16 && !ACN_TRAIN_AMP
-    // as fwd_layer: the NT input tiles' chains interleaved per k-step, operands read first; dX is the accumulator
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti) dX[ti] = 0.0f;
-#pragma unroll
-    for (int s = 0; s < 2 * KT; ++s) {
-        if (32 * (s >> 1) + 16 * (s & 1) >= NROW) continue;
-        f16x8 ahi[NT], alo[NT];
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti) {
-            const int o = (32 * (s >> 1) + 16 * (s & 1) + trow) * ld + 32 * ti + tcol;
-            ahi[ti] = cat44(ds_read_tr16(Wh + o), ds_read_tr16(Wh + o + 8 * ld));
-            alo[ti] = cat44(ds_read_tr16(Wlo + o), ds_read_tr16(Wlo + o + 8 * ld));
-        }
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti) dX[ti] = mfma_h(alo[ti], bh[s], dX[ti]);
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti) dX[ti] = mfma_h(ahi[ti], bl[s], dX[ti]);
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti) dX[ti] = mfma_h(ahi[ti], bh[s], dX[ti]);
-    }
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dX[ti][r] = dX[ti][r] * usc;
-    return;
-#endif
-#if ACN_MLP_KPIPE && ACN_BWD_TR16 && !ACN_TRAIN_AMP
     // as fwd_layer: the next live k-step's A operands are read while this k-step's MFMAs run (same chain, order)
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti) {
@@ -502,48 +432,7 @@ __device__ __forceinline__ void bwd_layer(const float* W, int ld, const f32x16 (
 #pragma unroll
         for (int r = 0; r < 16; ++r) dX[ti][r] = acc[r] * usc;
     }
-    return;
 #endif
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti) {
-        f32x16 acc = 0.0f;
-#pragma unroll
-        for (int s = 0; s < 2 * KT; ++s) {
-            if (32 * (s >> 1) + 16 * (s & 1) >= NROW) continue;
-            f16x8 ahi, alo;
-#if ACN_BWD_TR16
-            {
-                const int o = (32 * (s >> 1) + 16 * (s & 1) + trow) * ld + 32 * ti + tcol;
-                ahi = cat44(ds_read_tr16(Wh + o), ds_read_tr16(Wh + o + 8 * ld));
-#if !ACN_TRAIN_AMP
-                alo = cat44(ds_read_tr16(Wlo + o), ds_read_tr16(Wlo + o + 8 * ld));
-#endif
-            }
-#else
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int o = xrow(s, h, e) * ld + 32 * ti + i;
-                ahi[e] = Wh[o];
-                alo[e] = Wlo[o];
-            }
-#endif
-#if ACN_TRAIN_AMP
-            (void)alo;
-            acc = mfma_h(ahi, bh[s], acc);
-#else
-            acc = mfma_h(alo, bh[s], acc);
-            acc = mfma_h(ahi, bl[s], acc);
-            acc = mfma_h(ahi, bh[s], acc);
-#endif
-        }
-#if ACN_TRAIN_AMP
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dX[ti][r] = amp_r(acc[r]);
-#else
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dX[ti][r] = acc[r] * usc;
-#endif
-    }
 }
 #else
 // Y[to] (rows 32to..) = b + W . X  (W: 32*NT padded rows, ld = stride; X: KT input tiles).  The A operands
@@ -677,16 +566,11 @@ __device__ __forceinline__ void tile_forward(const float* Wl, const float* h0, c
     fwd_layer<1, 2, 32>(Wl + L_WC2, S64, Wl + L_BC2, C2, Rg, lane);
 }
 
-#ifndef ACN_FWD_VLOAD
-#define ACN_FWD_VLOAD 0   // mlp_fwd_kernel<false>: the producers' vector h0 / SH loads below (0: per-element loads)
-#endif
-#ifndef ACN_DW_PIPE
-#define ACN_DW_PIPE 1   // dw_blocks (fp32 stage): next k-step's LDS reads in flight, blocks' MFMAs interleaved
-#endif
 // Prefetched per-sample inputs of the producer waves (mlp_bwd_dw_pc_kernel): whole 16-B vectors at a clamped
 // sample index (no per-element exec branches), issued well ahead of their use and masked for samples past the
 // end only where they are consumed -- a scheduling barrier after the loads keeps the compiler from sinking them
-// to their uses.  The values are those load_tiles / tile_forward / dw_round's output-gradient reads take.
+// to their uses.  The values are those load_tiles / tile_forward and the per-element output / output-gradient
+// reads of mlp_bwd_kernel take.
 struct X0Raw {
     float4 v[4];   // h0 row elements rho(4q .. 4q + 3, h) = 8q + 4h + 0..3
 };
@@ -708,7 +592,6 @@ struct PcIn {      // issued after the forward's first layer (its h0 tile's regi
     float s[9];    // SH row value of accumulator row r = 7 .. 15 (rho(r, h) - 15, clamped; rows r < 7 are geo)
     float o[3], g[3];   // outputs / output gradients: h == 0 lanes rgb, h == 1 lanes sigma (in all three)
 };
-template <bool OG>   // OG: also the output / output-gradient values (the backward's producers)
 __device__ __forceinline__ void load_pcin(const float* __restrict__ sh, const float* __restrict__ out,
                                           const float* __restrict__ gout, int64_t m, bool ok, int h, PcIn& in) {
     const int64_t mc = ok ? m : 0;
@@ -717,12 +600,10 @@ __device__ __forceinline__ void load_pcin(const float* __restrict__ sh, const fl
         const int f = rho(r, h) - 15;
         in.s[r - 7] = sh[mc * 16 + (f < 0 ? 0 : (f > 15 ? 15 : f))];
     }
-    if (OG) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            in.o[c] = out[mc * 4 + (h ? 3 : c)];
-            in.g[c] = gout[mc * 4 + (h ? 3 : c)];
-        }
+    for (int c = 0; c < 3; ++c) {
+        in.o[c] = out[mc * 4 + (h ? 3 : c)];
+        in.g[c] = gout[mc * 4 + (h ? 3 : c)];
     }
 }
 __device__ __forceinline__ float opaque_f(float v) {   // pins a prefetched value's first use (and its wait) here
@@ -731,7 +612,6 @@ __device__ __forceinline__ float opaque_f(float v) {   // pins a prefetched valu
 }
 // tile_forward on a prefetched h0 tile, issuing the SH / output loads behind the first layer (bitwise the same
 // layers and values)
-template <bool OG = true>
 __device__ __forceinline__ void tile_forward_x(const float* Wl, const X0Raw& x0, const float* __restrict__ sh,
                                                const float* __restrict__ out, const float* __restrict__ gout,
                                                int64_t m, bool ok, int lane, PcIn& in, f32x16 (&A1)[2],
@@ -745,7 +625,7 @@ __device__ __forceinline__ void tile_forward_x(const float* Wl, const X0Raw& x0,
     }
     relu<2>(A1);
     __builtin_amdgcn_sched_barrier(0);
-    load_pcin<OG>(sh, out, gout, m, ok, h, in);
+    load_pcin(sh, out, gout, m, ok, h, in);
     __builtin_amdgcn_sched_barrier(0);
     fwd_layer<2, 2, 64>(Wl + L_W1, S64, Wl + L_B1, A1, A2, lane);
     relu<2>(A2);
@@ -786,15 +666,7 @@ __global__ void __launch_bounds__(SAVE ? 256 : 512) mlp_fwd_kernel(const float* 
         f32x16 X0[1], A1[2], A2[2], Hd[1], Cin[1], C1[2], C2[2], Rg[1];
         // opaque base: the LDS weight reads are re-issued per tile instead of hoisted out of the loop into
         // ~240 held registers (one wave per SIMD; with it the no-save form fits two)
-        if (!SAVE && ACN_FWD_VLOAD) {   // vector loads of h0, SH behind the first layer (no per-element branches)
-            X0Raw x0;
-            load_x0raw(h0, m, ok, h, x0);
-            PcIn in;
-            tile_forward_x<false>(Wl + opaque_s(0), x0, sh, nullptr, nullptr, m, ok, lane, in, A1, A2, Hd, Cin, C1,
-                                  C2, Rg);
-        } else {
-            tile_forward(Wl + opaque_s(0), h0, sh, m, ok, lane, X0, A1, A2, Hd, Cin, C1, C2, Rg);
-        }
+        tile_forward(Wl + opaque_s(0), h0, sh, m, ok, lane, X0, A1, A2, Hd, Cin, C1, C2, Rg);
         if (ok) {
             if (h == 0) {
 #pragma unroll
@@ -901,11 +773,11 @@ __global__ void __launch_bounds__(256) mlp_bwd_kernel(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Fused backward with the weight gradients (acn_mlp_train_bwd_dw).  A workgroup of 4 waves takes 4 tiles
-// (128 samples) per round; each wave re-runs the forward of its tile from h0 / sh (the same tile_forward
-// as mlp_fwd_kernel, so the activations are bit-identical) instead of reading saved activations, and runs
-// the backward chain layer by layer.  At each layer the 4 waves put dY and X of their tiles into one
-// shared LDS stage [feature][128 samples]; after a barrier, wave w forms its share of that layer's
+// Fused backward with the weight gradients (acn_mlp_train_bwd_dw, mlp_bwd_dw_pc_kernel below).  A workgroup
+// takes 4 tiles (128 samples) per round.  Its four producer waves each re-run the forward of one tile from
+// h0 / sh (the layers of mlp_fwd_kernel, so the activations are bit-identical) instead of reading saved
+// activations, and run the backward chain layer by layer.  At each layer they put dY and X of their tiles into
+// one shared LDS stage [feature][128 samples]; after a barrier, consumer wave w forms its share of that layer's
 // [dW | db] over all 128 samples on v_mfma_f32_16x16x4_f32 (row block w of the 64-row layers, column
 // block w of the sigma / colour heads), accumulating in registers that live for the whole kernel:
 // every gradient element has exactly one owner wave, so there are no atomics, and a workgroup writes
@@ -931,122 +803,55 @@ __device__ __forceinline__ void relu_mask(f32x16 (&G)[NT], const f32x16 (&Y)[NT]
         for (int r = 0; r < 16; ++r) G[t][r] = Y[t][r] > 0.0f ? G[t][r] : 0.0f;
 }
 
-#ifndef ACN_DW_F16X3
-// weight-gradient contraction on the fp16x3 split as well.  Off: measured slower (fused backward 352 ->
-// 383 us at M = 384k, meta step 79.1 -> 82.8 ms): with one wave per SIMD the dW phase is bound by the
-// staging (split + two f16 planes written per element) and LDS traffic, not by the fp32 MFMAs it saves.
-// The AMP build always takes the fp16 stage with ONE plane: its dY and X are fp16 values already, so one
-// v_mfma_f32_16x16x16_f16 product per term is exact (fp32 accumulation), as autocast's fp16 GEMM computes it
-#define ACN_DW_F16X3 ACN_TRAIN_AMP
-#endif
-#if ACN_TRAIN_AMP && !ACN_DW_F16X3
-#error "the AMP build contracts [dW | db] on the fp16 stage"
-#endif
-constexpr int kStagePlanes = ACN_TRAIN_AMP ? 1 : 2;   // fp16 stage: hi (+ lo for the fp16x3 split)
-#ifndef ACN_DW_CSPLIT
-#define ACN_DW_CSPLIT 0   // fp32 stage, fp16x3 split by the consumer waves (producer / consumer kernel only)
-#endif
-#if ACN_DW_CSPLIT && (ACN_DW_F16X3 || !ACN_TRAIN_F16X3)
-#error "ACN_DW_CSPLIT is a variant of the default build's fp32-stage backward"
-#endif
-
-struct StageScale {
-    int kY, kX;  // power-of-two exponents the staged dY / X carry (0: unscaled fp32 stage)
-};
-
-#if ACN_DW_F16X3
-// ---- fp16x3 weight gradients.  The stage holds f16 planes (hi, then lo) of [144 rows][SH halves]:
-// rows 0..63 dY, 64..127 X, row 128 ones (rows 129..143 zero) -- the bias sums come out of the MFMA as
-// the contraction with the ones row.  dY and X are scaled by workgroup-uniform powers of two (the
-// contraction mixes the four waves' samples): each wave publishes its max |dY| and max |X| before the
-// stage barrier and all waves take the maximum of the four.  Per round and block the 128-sample
-// contraction is 8 k-steps of v_mfma_f32_16x16x16_f16 x 3 products into a temporary, added to the
-// persistent fp32 accumulator times 2^-(kY + kX).
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+// ---- the stage and its contraction.  The default and exact builds stage fp32 values and contract them on
+// v_mfma_f32_16x16x4_f32.  (Staging an fp16x3 split instead, by the producers as two f16 planes or by the
+// consumers as they read, measured slower both ways: the dW phase is bound by the staging and the LDS traffic,
+// not by the fp32 MFMAs that saves; docs/DESIGN_HISTORY.md 4i.)  The AMP build stages one plane of fp16 values:
+// its dY and X are fp16 values already, so one v_mfma_f32_16x16x16_f16 product per term is exact (fp32
+// accumulation), as autocast's fp16 GEMM computes it -- unscaled, what autocast's GEMM sees.
+#if ACN_TRAIN_AMP
+// The stage holds one f16 plane of [144 rows][SH halves]: rows 0..63 dY, 64..127 X, row 128 ones (rows
+// 129..143 zero) -- the bias sums come out of the MFMA as the contraction with the ones row.  Per round and
+// block the 128-sample contraction is 8 k-steps of v_mfma_f32_16x16x16_f16 into a temporary, added to the
+// persistent fp32 accumulator.
 constexpr int SH = 136;                   // stage row stride (halves): 128 samples + 8, 16-B aligned rows
 constexpr int ST_ROWS = 144, ST_ONES = 128;
-constexpr int ST_FLOATS = kStagePlanes * ST_ROWS * SH / 2;  // one or two f16 planes
+constexpr int ST_FLOATS = ST_ROWS * SH / 2;
 __device__ __forceinline__ f32x4 mfma16h(const f16x4& a, const f16x4& b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
 }
 typedef f32x4 BiasAcc;
 
-__device__ __forceinline__ void stage_init(float* st) {  // the ones row (both planes zero elsewhere there)
+__device__ __forceinline__ void stage_init(float* st) {  // the ones row (zero elsewhere there)
     _Float16* hp = reinterpret_cast<_Float16*>(st);
-    _Float16* lp = hp + ST_ROWS * SH;
-    for (int e = threadIdx.x; e < (ST_ROWS - ST_ONES) * SH; e += blockDim.x) {
+    for (int e = threadIdx.x; e < (ST_ROWS - ST_ONES) * SH; e += blockDim.x)
         hp[ST_ONES * SH + e] = (_Float16)(e < SH ? 1.0f : 0.0f);
-        if (kStagePlanes == 2) lp[ST_ONES * SH + e] = (_Float16)0.0f;
-    }
 }
 
-// max |x| bits of this wave's tiles (wave-uniform; DPP + readlanes)
+// rows of accumulator-layout tiles -> stage[row0 + feature][32 * w + sample], rounded to fp16
 template <int NT>
-__device__ __forceinline__ uint32_t wave_absmax_bits(const f32x16 (&T)[NT]) {
-    uint32_t m = 0u;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const uint32_t b = __float_as_uint(T[t][r]) & 0x7fffffffu;
-            m = b > m ? b : m;
-        }
-    auto dmax = [](uint32_t v, uint32_t w) { return v > w ? v : w; };
-    m = dmax(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, false));
-    m = dmax(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, false));
-    m = dmax(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, false));
-    m = dmax(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, false));
-    return dmax(dmax((uint32_t)__builtin_amdgcn_readlane((int)m, 0), (uint32_t)__builtin_amdgcn_readlane((int)m, 16)),
-                dmax((uint32_t)__builtin_amdgcn_readlane((int)m, 32), (uint32_t)__builtin_amdgcn_readlane((int)m, 48)));
-}
-__device__ __forceinline__ int exp_for_bits(uint32_t w) {  // as tile_scale_exp
-    if (w == 0u || w >= 0x7f800000u) return 0;
-    const int be = (int)(w >> 23);
-    const int k = 14 - ((be == 0 ? -126 : be - 127) + 1);
-    return k > 100 ? 100 : (k < -100 ? -100 : k);
-}
-
-template <int NT>
-__device__ __forceinline__ void stage_put(float* st, int row0, const f32x16 (&T)[NT], int k, int w, int lane) {
+__device__ __forceinline__ void stage_put(float* st, int row0, const f32x16 (&T)[NT], int w, int lane) {
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     _Float16* hp = reinterpret_cast<_Float16*>(st);
-    _Float16* lp = hp + ST_ROWS * SH;
     const int j = lane & 31, h = lane >> 5;
-    const float sc = ldexpf(1.0f, k);
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
-            const f32x2 x = (f32x2){T[t][r], T[t][r + 1]} * (f32x2){sc, sc};
-            const f16x2 hi = __builtin_convertvector(x, f16x2);
-            const int o0 = (row0 + 32 * t + rho(r, h)) * SH + 32 * w + j, o1 = (row0 + 32 * t + rho(r + 1, h)) * SH + 32 * w + j;
-            hp[o0] = hi[0];
-            hp[o1] = hi[1];
-            if (kStagePlanes == 2) {
-                const f16x2 lo = __builtin_convertvector(x - __builtin_convertvector(hi, f32x2), f16x2);
-                lp[o0] = lo[0];
-                lp[o1] = lo[1];
-            }
+            const f16x2 hi = __builtin_convertvector(((f32x2){T[t][r], T[t][r + 1]}), f16x2);
+            hp[(row0 + 32 * t + rho(r, h)) * SH + 32 * w + j] = hi[0];
+            hp[(row0 + 32 * t + rho(r + 1, h)) * SH + 32 * w + j] = hi[1];
         }
-}
-// the producer / consumer kernel's put (AMP: unscaled fp16 values)
-template <int NT>
-__device__ __forceinline__ void stage_put(float* st, int row0, const f32x16 (&T)[NT], int w, int lane) {
-    stage_put<NT>(st, row0, T, 0, w, lane);
 }
 
 // acc[n] += dY[16 rows from arow] . X[16 features from xrow + 16 n]^T over the 128 staged samples,
 // bacc (column 0) += the dY rows' sums; lane (i = l & 15, q = l >> 4) supplies k-elements = samples
 // 32 q + 4 t + 0..3 of k-step t
-template <int NCB, bool PIPE = false>   // PIPE: the fp32 stage's option (unused on the fp16 stage)
+template <int NCB, bool PIPE>   // PIPE: the fp32 stage's option (unused here)
 __device__ __forceinline__ void dw_blocks(const float* st, int arow, int xrow, f32x4 (&acc)[NCB], BiasAcc& bacc,
-                                          StageScale sc, int lane) {
-#if ACN_DIAG_NODW  // diagnostic build only: no weight-gradient contraction
-    return;
-#endif
+                                          int lane) {
     const _Float16* hp = reinterpret_cast<const _Float16*>(st);
-    const _Float16* lp = hp + ST_ROWS * SH;
     const int i = lane & 15, q = lane >> 4;
     const int oa = (arow + i) * SH + 32 * q, ob = (xrow + i) * SH + 32 * q, oo = (ST_ONES + i) * SH + 32 * q;
     f32x4 tmp[NCB], tb = 0.0f;
@@ -1056,66 +861,19 @@ __device__ __forceinline__ void dw_blocks(const float* st, int arow, int xrow, f
     for (int t = 0; t < 8; ++t) {
         const f16x4 ah = *reinterpret_cast<const f16x4*>(hp + oa + 4 * t);
         const f16x4 on = *reinterpret_cast<const f16x4*>(hp + oo + 4 * t);
-        if (kStagePlanes == 2) {
-            const f16x4 al = *reinterpret_cast<const f16x4*>(lp + oa + 4 * t);
-            tb = mfma16h(al, on, tb);
-            tb = mfma16h(ah, on, tb);
+        tb = mfma16h(ah, on, tb);
 #pragma unroll
-            for (int n = 0; n < NCB; ++n) {
-                const f16x4 bh = *reinterpret_cast<const f16x4*>(hp + ob + 16 * n * SH + 4 * t);
-                const f16x4 bl = *reinterpret_cast<const f16x4*>(lp + ob + 16 * n * SH + 4 * t);
-                tmp[n] = mfma16h(al, bh, tmp[n]);
-                tmp[n] = mfma16h(ah, bl, tmp[n]);
-                tmp[n] = mfma16h(ah, bh, tmp[n]);
-            }
-        } else {   // AMP: dY, X are fp16 values -- one exact product per term
-            tb = mfma16h(ah, on, tb);
-#pragma unroll
-            for (int n = 0; n < NCB; ++n) {
-                const f16x4 bh = *reinterpret_cast<const f16x4*>(hp + ob + 16 * n * SH + 4 * t);
-                tmp[n] = mfma16h(ah, bh, tmp[n]);
-            }
+        for (int n = 0; n < NCB; ++n) {
+            const f16x4 bh = *reinterpret_cast<const f16x4*>(hp + ob + 16 * n * SH + 4 * t);
+            tmp[n] = mfma16h(ah, bh, tmp[n]);
         }
     }
-    const float ua = ldexpf(1.0f, -sc.kY), uab = ldexpf(1.0f, -(sc.kY + sc.kX));
 #pragma unroll
     for (int n = 0; n < NCB; ++n)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[n][r] = __builtin_fmaf(tmp[n][r], uab, acc[n][r]);
+        for (int r = 0; r < 4; ++r) acc[n][r] += tmp[n][r];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) bacc[r] = __builtin_fmaf(tb[r], ua, bacc[r]);
-}
-
-// one layer's stage round: publish this wave's maxima, barrier (previous readers done, maxima visible),
-// put dY / X scaled by the workgroup maxima, barrier
-template <int NO, int NI>
-__device__ __forceinline__ StageScale stage_layer(float* st, const f32x16 (&dY)[NO], const f32x16 (&X)[NI], int w,
-                                                  int lane) {
-#if ACN_TRAIN_AMP   // fp16 values already: no rescaling (what autocast's GEMM sees)
-    __syncthreads();
-    stage_put<NO>(st, 0, dY, 0, w, lane);
-    stage_put<NI>(st, X_ROW, X, 0, w, lane);
-    __syncthreads();
-    return StageScale{0, 0};
-#endif
-    __shared__ uint32_t smax[8];
-    const uint32_t my = wave_absmax_bits<NO>(dY), mx = wave_absmax_bits<NI>(X);
-    if (lane == 0) {
-        smax[w] = my;
-        smax[4 + w] = mx;
-    }
-    __syncthreads();
-    uint32_t ay = 0u, ax = 0u;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        ay = smax[v] > ay ? smax[v] : ay;
-        ax = smax[4 + v] > ax ? smax[4 + v] : ax;
-    }
-    const StageScale sc{exp_for_bits(ay), exp_for_bits(ax)};
-    stage_put<NO>(st, 0, dY, sc.kY, w, lane);
-    stage_put<NI>(st, X_ROW, X, sc.kX, w, lane);
-    __syncthreads();
-    return sc;
+    for (int r = 0; r < 4; ++r) bacc[r] += tb[r];
 }
 #else
 constexpr int ST_FLOATS = 128 * SW;
@@ -1129,99 +887,18 @@ __device__ __forceinline__ void stage_put(float* st, int row0, const f32x16 (&T)
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) st[(row0 + 32 * t + rho(r, h)) * SW + 32 * w + j] = amp_r(T[t][r]);  // AMP: fp16 X
+        for (int r = 0; r < 16; ++r) st[(row0 + 32 * t + rho(r, h)) * SW + 32 * w + j] = T[t][r];
 }
-
-#if ACN_DW_CSPLIT
-// Consumer-side fp16x3 (ACN_DW_CSPLIT): the producers put fp32 values as before and publish the layer's
-// workgroup max |dY| / |X| (pc_publish); each consumer scales what it reads by those powers of two, splits
-// into hi / lo fp16 and contracts on v_mfma_f32_16x16x16_f16 (hi*hi + hi*lo + lo*hi): one MFMA per product
-// term covers the 16 samples the four fp32 16x16x4 MFMAs did.  The bias sums stay the exact fp32 VALU sums.
-typedef _Float16 f16x4d __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma16hd(const f16x4d& a, const f16x4d& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-}
-template <int NT>
-__device__ __forceinline__ uint32_t wave_absmax_bits(const f32x16 (&T)[NT]) {
-    uint32_t m = 0u;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const uint32_t b = __float_as_uint(T[t][r]) & 0x7fffffffu;
-            m = b > m ? b : m;
-        }
-    auto dmax = [](uint32_t v, uint32_t w) { return v > w ? v : w; };
-    m = dmax(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, false));
-    m = dmax(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, false));
-    m = dmax(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, false));
-    m = dmax(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, false));
-    return dmax(dmax((uint32_t)__builtin_amdgcn_readlane((int)m, 0), (uint32_t)__builtin_amdgcn_readlane((int)m, 16)),
-                dmax((uint32_t)__builtin_amdgcn_readlane((int)m, 32), (uint32_t)__builtin_amdgcn_readlane((int)m, 48)));
-}
-__device__ __forceinline__ int exp_for_bits(uint32_t w) {  // as tile_scale_exp
-    if (w == 0u || w >= 0x7f800000u) return 0;
-    const int be = (int)(w >> 23);
-    const int k = 14 - ((be == 0 ? -126 : be - 127) + 1);
-    return k > 100 ? 100 : (k < -100 ? -100 : k);
-}
-__device__ __forceinline__ void split4(const f32x4& x, float sc, f16x4d& hi, f16x4d& lo) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const f32x2 v = (f32x2){x[2 * u], x[2 * u + 1]} * (f32x2){sc, sc};
-        const f16x2 h = __builtin_convertvector(v, f16x2);
-        const f16x2 l = __builtin_convertvector(v - __builtin_convertvector(h, f32x2), f16x2);
-        hi[2 * u] = h[0];
-        hi[2 * u + 1] = h[1];
-        lo[2 * u] = l[0];
-        lo[2 * u + 1] = l[1];
-    }
-}
-#endif
 
 // acc[n] += dY[16 rows from arow] . X[16 features from xrow + 16 n]^T over the 128 staged samples;
 // lane (i = l & 15, q = l >> 4) supplies k = sample 32 q + kk (4 k-steps per 16-B read).  bsum += this
 // lane's share of the bias row sum (the A operand is dY itself).
-template <int NCB, bool PIPE = (ACN_DW_PIPE != 0)>
+template <int NCB, bool PIPE>
 __device__ __forceinline__ void dw_blocks(const float* st, int arow, int xrow, f32x4 (&acc)[NCB], float& bsum,
-                                          StageScale sc, int lane) {
-#if ACN_DIAG_NODW  // diagnostic build only: no weight-gradient contraction
-    return;
-#endif
+                                          int lane) {
     const int i = lane & 15, q = lane >> 4;
     const float* pa = st + (arow + i) * SW + 32 * q;
     const float* pb = st + (xrow + i) * SW + 32 * q;
-#if ACN_DW_CSPLIT
-    const float sa = ldexpf(1.0f, sc.kY), sb = ldexpf(1.0f, sc.kX), uab = ldexpf(1.0f, -(sc.kY + sc.kX));
-    f32x4 tmp[NCB];
-#pragma unroll
-    for (int n = 0; n < NCB; ++n) tmp[n] = 0.0f;
-#pragma unroll
-    for (int k4 = 0; k4 < 8; ++k4) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(pa + 4 * k4);
-        bsum += (a[0] + a[1]) + (a[2] + a[3]);
-        f16x4d ah, al;
-        split4(a, sa, ah, al);
-#pragma unroll
-        for (int n = 0; n < NCB; ++n) {
-            const f32x4 b = *reinterpret_cast<const f32x4*>(pb + 16 * n * SW + 4 * k4);
-            f16x4d bh, bl;
-            split4(b, sb, bh, bl);
-            tmp[n] = mfma16hd(al, bh, tmp[n]);
-            tmp[n] = mfma16hd(ah, bl, tmp[n]);
-            tmp[n] = mfma16hd(ah, bh, tmp[n]);
-        }
-    }
-#pragma unroll
-    for (int n = 0; n < NCB; ++n)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[n][r] = __builtin_fmaf(tmp[n][r], uab, acc[n][r]);
-    return;
-#else
-    (void)sc;
-#endif
     if (PIPE) {
     // software-pipelined: the next k-step's A / B vectors are read while this one's MFMAs run, and the MFMAs
     // of the NCB independent blocks alternate (each block's own chain keeps its k order: the same sums bit for
@@ -1265,36 +942,6 @@ __device__ __forceinline__ void dw_blocks(const float* st, int arow, int xrow, f
         }
     }
 }
-
-// one layer's stage round: barrier (previous readers done), put dY / X, barrier
-template <int NO, int NI>
-__device__ __forceinline__ StageScale stage_layer(float* st, const f32x16 (&dY)[NO], const f32x16 (&X)[NI], int w,
-                                                  int lane) {
-#if ACN_DW_CSPLIT   // the workgroup's max |dY| / |X| travel with the stage (the consumer-side split's scales)
-    __shared__ uint32_t smax_c[8];
-    const uint32_t my = wave_absmax_bits<NO>(dY), mx = wave_absmax_bits<NI>(X);
-    if (lane == 0) {
-        smax_c[w] = my;
-        smax_c[4 + w] = mx;
-    }
-#endif
-    __syncthreads();
-#if ACN_DW_CSPLIT   // read between the barriers: no wave can overwrite them (next layer) before all have read
-    uint32_t ay = 0u, ax = 0u;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        ay = smax_c[v] > ay ? smax_c[v] : ay;
-        ax = smax_c[4 + v] > ax ? smax_c[4 + v] : ax;
-    }
-#endif
-    stage_put<NO>(st, 0, dY, w, lane);
-    stage_put<NI>(st, X_ROW, X, w, lane);
-    __syncthreads();
-#if ACN_DW_CSPLIT
-    return StageScale{exp_for_bits(ay), exp_for_bits(ax)};
-#endif
-    return StageScale{0, 0};
-}
 #endif
 
 // D (16x16x4 layout: lane l, reg r = row 4 (l >> 4) + r, col l & 15) of one block -> dst rows / cols
@@ -1326,132 +973,6 @@ __device__ __forceinline__ void dw_zero(DwAcc& a) {
     a.bWC2 = a.bWC1 = a.bWC0 = a.bHD = a.bW1 = a.bW0 = 0.0f;
 }
 
-#ifndef ACN_DW_PC
-#define ACN_DW_PC 1  // mlp_bwd_dw_pc_kernel (producer / consumer waves) for acn_mlp_train_bwd_dw
-#endif
-#ifndef ACN_DW_DIAG
-#define ACN_DW_DIAG 0  // diagnostic builds: shader-clock cycles per phase of mlp_bwd_dw_kernel (acn_mlp_dw_diag)
-#endif
-#if ACN_DW_DIAG
-__device__ unsigned long long g_dw_diag[MAX_DW_BLOCKS * 4][8];
-struct DwClock {
-    uint64_t c[8];
-    uint64_t t;
-};
-#define DW_T0(dc) (dc).t = __builtin_amdgcn_s_memtime()
-#define DW_LAP(dc, i)                                              \
-    do {                                                           \
-        const uint64_t now_ = __builtin_amdgcn_s_memtime();        \
-        (dc).c[i] += now_ - (dc).t;                                \
-        (dc).t = now_;                                             \
-    } while (0)
-#else
-struct DwClock {};
-#define DW_T0(dc) (void)0
-#define DW_LAP(dc, i) (void)0
-#endif
-
-// one round: wave w re-runs the forward of its tile (samples m = tile * 32 + j), runs the backward chain
-// and adds its share of every layer's [dW | db] over the workgroup's 128 samples; barriers inside
-__device__ __forceinline__ void dw_round(const float* W, float* st, const float* __restrict__ h0,
-                                         const float* __restrict__ sh, const float* __restrict__ out,
-                                         const float* __restrict__ gout, int64_t m, bool ok, int w, int lane,
-                                         float* __restrict__ gh0, DwAcc& a, DwClock& dc) {
-    const int h = lane >> 5;
-    f32x16 A1[2], A2[2], Hd[1], Cin[1], C1[2], C2[2], Rg[1];
-    DW_T0(dc);
-    {
-        f32x16 X0[1];
-        tile_forward(W, h0, sh, m, ok, lane, X0, A1, A2, Hd, Cin, C1, C2, Rg);
-    }
-    DW_LAP(dc, 0);
-    f32x16 dRg[1], dHd[1];
-    dRg[0] = 0.0f;
-    float dsig = 0.0f;
-    if (ok) {
-        if (h == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float y = out[m * 4 + c];
-                dRg[0][c] = grad_rgb(gout[m * 4 + c], y);
-            }
-        } else {
-            dsig = grad_sigma(gout[m * 4 + 3], out[m * 4 + 3]);
-        }
-    }
-    DW_LAP(dc, 4);
-    // colour head 3 x 64: column block w, rows 0..15 (0..2 live)
-    {
-        const StageScale sc = stage_layer<1, 2>(st, dRg, C2, w, lane);
-        DW_LAP(dc, 1);
-        dw_blocks<1>(st, 0, X_ROW + 16 * w, a.aWC2, a.bWC2, sc, lane);
-        DW_LAP(dc, 2);
-    }
-    f32x16 G2[2], G1[2], Gc[1];
-    bwd_layer<2, 1, 3, 32>(W + L_WC2, S64, dRg, G2, lane);
-    relu_mask<2>(G2, C2);
-    DW_LAP(dc, 3);
-    // colour layer 1, 64 x 64: row block w
-    {
-        const StageScale sc = stage_layer<2, 2>(st, G2, C1, w, lane);
-        DW_LAP(dc, 1);
-        dw_blocks<4>(st, 16 * w, X_ROW, a.aWC1, a.bWC1, sc, lane);
-        DW_LAP(dc, 2);
-    }
-    bwd_layer<2, 2, 64, 64>(W + L_WC1, S64, G2, G1, lane);
-    relu_mask<2>(G1, C1);
-    DW_LAP(dc, 3);
-    // colour layer 0, 64 x 31 (input 31 = zero column): row block w
-    {
-        const StageScale sc = stage_layer<2, 1>(st, G1, Cin, w, lane);
-        DW_LAP(dc, 1);
-        dw_blocks<2>(st, 16 * w, X_ROW, a.aWC0, a.bWC0, sc, lane);
-        DW_LAP(dc, 2);
-    }
-    bwd_layer<1, 2, 64, 64>(W + L_WC0, S32, G1, Gc, lane);  // d cin: rows 0..14 = d geo (SH rows dropped)
-    DW_LAP(dc, 3);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int f = rho(r, h);
-        dHd[0][r] = f < 15 ? Gc[0][r] : (f == 15 ? dsig : 0.0f);
-    }
-    // heads [geo 15 | sigma 1] x 64: column block w
-    {
-        const StageScale sc = stage_layer<1, 2>(st, dHd, A2, w, lane);
-        DW_LAP(dc, 1);
-        dw_blocks<1>(st, 0, X_ROW + 16 * w, a.aHD, a.bHD, sc, lane);
-        DW_LAP(dc, 2);
-    }
-    f32x16 GA2[2], GA1[2], GH[1];
-    bwd_layer<2, 1, 16, 32>(W + L_WH, S64, dHd, GA2, lane);
-    relu_mask<2>(GA2, A2);
-    DW_LAP(dc, 3);
-    // sigma trunk 1, 64 x 64: row block w
-    {
-        const StageScale sc = stage_layer<2, 2>(st, GA2, A1, w, lane);
-        DW_LAP(dc, 1);
-        dw_blocks<4>(st, 16 * w, X_ROW, a.aW1, a.bW1, sc, lane);
-        DW_LAP(dc, 2);
-    }
-    bwd_layer<2, 2, 64, 64>(W + L_W1, S64, GA2, GA1, lane);
-    relu_mask<2>(GA1, A1);
-    DW_LAP(dc, 3);
-    // sigma trunk 0, 64 x 32: row block w
-    f32x16 X0[1];
-    load_tiles<1>(h0, 32, 0, 32, m, ok, h, X0);  // reloaded (L2-hot) rather than kept live
-    {
-        const StageScale sc = stage_layer<2, 1>(st, GA1, X0, w, lane);
-        DW_LAP(dc, 1);
-        dw_blocks<2>(st, 16 * w, X_ROW, a.aW0, a.bW0, sc, lane);
-        DW_LAP(dc, 2);
-    }
-    if (gh0) {
-        bwd_layer<1, 2, 64, 64>(W + L_W0, S32, GA1, GH, lane);
-        store_tiles<1>(gh0, 32, 0, 32, m, ok, h, GH);
-    }
-    DW_LAP(dc, 5);
-}
-
 // one copy of the 13,715 partial sums: every element has exactly one owner (wave, lane, register)
 __device__ __forceinline__ void dw_flush(DwAcc& a, float* __restrict__ dst, int w, int lane0) {
     const int cw = 16 * w;
@@ -1471,7 +992,7 @@ __device__ __forceinline__ void dw_flush(DwAcc& a, float* __restrict__ dst, int 
         });
         flush_block(a.aW0[n], lane0, [&](int o, int c, float v) { dst[D_W0 + 32 * (cw + o) + 16 * n + c] = v; });
     }
-#if ACN_DW_F16X3
+#if ACN_TRAIN_AMP
     // bias rows = column 0 of the ones-row contraction blocks: lanes 0, 16, 32, 48 hold rows 4 (l >> 4) + r
     if ((lane0 & 15) == 0) {
 #pragma unroll
@@ -1506,144 +1027,44 @@ __device__ __forceinline__ void dw_flush(DwAcc& a, float* __restrict__ dst, int 
 #endif
 }
 
-__global__ void __launch_bounds__(256) mlp_bwd_dw_kernel(const float* __restrict__ img, const float* __restrict__ h0,
-                                                         const float* __restrict__ sh, const float* __restrict__ out,
-                                                         const float* __restrict__ gout, int64_t M,
-                                                         float* __restrict__ gh0, float* __restrict__ partial) {
-    __shared__ __attribute__((aligned(16))) float Wl[L_FLOATS];
-    __shared__ __attribute__((aligned(16))) float st_base[ST_FLOATS];
-    stage_weights(img, Wl);
-    stage_init(st_base);
-    __syncthreads();
-    const int lane0 = threadIdx.x & 63, j = lane0 & 31, w = threadIdx.x >> 6;
-    const int64_t ntiles = (M + 31) / 32;
-    DwAcc a;
-    dw_zero(a);
-    DwClock dc{};
-    // rounds are uniform over the workgroup (barriers inside): tiles past the end have zero gradients
-    for (int64_t base = (int64_t)blockIdx.x * 4; base < ntiles; base += (int64_t)gridDim.x * 4) {
-        const int64_t m = (base + w) * 32 + j;
-        dw_round(Wl + opaque_s(0), st_base + opaque_s(0), h0, sh, out, gout, m, m < M, w, opaque_v(lane0), gh0, a, dc);
-    }
-    DW_T0(dc);
-    dw_flush(a, partial + (int64_t)blockIdx.x * NDW, w, lane0);
-#if ACN_DW_DIAG
-    DW_LAP(dc, 6);
-    if (lane0 == 0)
-        for (int i = 0; i < 8; ++i) g_dw_diag[blockIdx.x * 4 + w][i] = dc.c[i];
-#endif
-}
-
-// Producer / consumer form of the fused backward (8-wave workgroups, two waves per SIMD).  Waves 0-3
-// (producers) run exactly the per-tile work of dw_round -- forward recompute, the dX chain, ReLU masks --
-// and put each layer's dY / X into the shared stage; waves 4-7 (consumers) hold the weight-gradient
-// accumulators of the same row / column blocks wave w - 4 owned in dw_round and contract the stage.  Per
-// layer: producers put -> barrier -> [producers: dX of the layer | consumers: dW of the layer] -> barrier,
-// so the MFMA-bound contraction overlaps the producers' VALU-bound split / ReLU / dX work instead of
-// following it, and neither role carries the other's registers.  The barrier that frees the stage for the
-// next round sits at the HEAD of the producers' round (after the forward recompute), not at the end of the
-// previous one, so the consumers' last layer (sigma trunk 0) runs beside the producers' dL/dh0 and their next
-// forward recompute instead of in front of them.  Every wave executes the same barriers per
-// round and the same rounds; with the fp32 stage the sums, their order and every output are those of
-// mlp_bwd_dw_kernel bit for bit (same owners, same stage, same k order).
-//   fp16 stages: the AMP build puts fp16 values unscaled (one plane); the fp16x3 stage (ACN_DW_F16X3 in the
-// default build) scales dY and X by workgroup-uniform powers of two: each producer wave publishes its max
-// |dY| / |X| of the NEXT layer right after computing that layer's dY (before the barrier that ends the
-// current layer), into one of two alternating LDS slots -- so the consumers, which read the current layer's
-// exponents after its put barrier, never race the producers' next publish; one extra barrier per round
-// publishes the first layer's maxima.
-#ifndef ACN_DIAG_NOPROD
-#define ACN_DIAG_NOPROD 0
-#endif
-#if ACN_DIAG_NOPROD
-#define PC_BWD(...) (void)0
-#else
-#define PC_BWD(...) __VA_ARGS__
-#endif
-__device__ __forceinline__ void pc_sync() { __syncthreads(); }
-#ifndef ACN_DW_PRIO
-#define ACN_DW_PRIO 0   // wave priority in mlp_bwd_dw_pc_kernel: 1 producers raised, 2 consumers raised (A/B)
-#endif
-#ifndef ACN_DW_PREFETCH
-#define ACN_DW_PREFETCH 1   // producers: vector loads of h0 / SH / outputs issued ahead of their use (0: in place)
-#endif
-#ifndef ACN_DW_HEADSYNC
-#define ACN_DW_HEADSYNC 1   // the stage-free barrier at the head of the producers' round (0: at the end, round 5)
-#endif
-constexpr bool kPcScaled = (ACN_DW_F16X3 && !ACN_TRAIN_AMP) || ACN_DW_CSPLIT;
-
+// The roles (8-wave workgroups, two waves per SIMD).  Waves 0-3 (producers) each take one 32-sample tile of the
+// round: forward recompute, the dX chain, ReLU masks; they put each layer's dY / X into the shared stage, tile w
+// in stage columns 32 w .. 32 w + 31.  Waves 4-7 (consumers) hold the weight-gradient accumulators: consumer w
+// owns row block 16 w .. 16 w + 15 of the 64-row layers and column block 16 w .. of the two heads, and
+// contracts the stage over its 128 samples in a fixed k order (dw_blocks: every k-step takes one sample of each
+// lane quarter q out of that quarter's samples 32 q .. 32 q + 31, ascending).  Per layer: producers put ->
+// barrier -> [producers: dX of the layer | consumers: dW of the layer] -> barrier, so the MFMA-bound
+// contraction overlaps the producers' VALU-bound split / ReLU / dX work instead of following it, and neither
+// role carries the other's registers.  The barrier
+// that frees the stage for the next round sits at the HEAD of the producers' round (after the forward
+// recompute), not at the end of the previous one, so the consumers' last layer (sigma trunk 0) runs beside the
+// producers' dL/dh0 and their next forward recompute instead of in front of them.  Every wave executes the same
+// 12 barriers per round (the head barrier, one after each of the six puts, one after each of the first five
+// layers' dX / dW) and the same rounds.  The sums are deterministic: every element of [dW | db] has one owner
+// (wave, lane, register), which adds its rounds in order and each round's samples in the fixed k order above;
+// the workgroups' copies are added in index order (mlp_dw_reduce_kernel).  No atomics anywhere.
 template <int NO, int NI>
-__device__ __forceinline__ void pc_publish(uint32_t* smax, const f32x16 (&dY)[NO], const f32x16 (&X)[NI], int w,
-                                           int lane) {
-#if (ACN_DW_F16X3 && !ACN_TRAIN_AMP) || ACN_DW_CSPLIT
-    const uint32_t my = wave_absmax_bits<NO>(dY), mx = wave_absmax_bits<NI>(X);
-    if (lane == 0) {
-        smax[w] = my;
-        smax[4 + w] = mx;
-    }
-#else
-    (void)smax; (void)dY; (void)X; (void)w; (void)lane;
-#endif
-}
-__device__ __forceinline__ StageScale pc_scale(const uint32_t* smax) {
-#if (ACN_DW_F16X3 && !ACN_TRAIN_AMP) || ACN_DW_CSPLIT
-    uint32_t ay = 0u, ax = 0u;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        ay = smax[v] > ay ? smax[v] : ay;
-        ax = smax[4 + v] > ax ? smax[4 + v] : ax;
-    }
-    return StageScale{exp_for_bits(ay), exp_for_bits(ax)};
-#else
-    (void)smax;
-    return StageScale{0, 0};
-#endif
-}
-template <int NO, int NI>
-__device__ __forceinline__ void pc_put(float* st, const f32x16 (&dY)[NO], const f32x16 (&X)[NI], const uint32_t* smax,
-                                       int w, int lane) {
-#if ACN_DW_F16X3
-    const StageScale sc = pc_scale(smax);
-    stage_put<NO>(st, 0, dY, sc.kY, w, lane);
-    stage_put<NI>(st, X_ROW, X, sc.kX, w, lane);
-#else
-    (void)smax;
+__device__ __forceinline__ void pc_put(float* st, const f32x16 (&dY)[NO], const f32x16 (&X)[NI], int w, int lane) {
     stage_put<NO>(st, 0, dY, w, lane);
     stage_put<NI>(st, X_ROW, X, w, lane);
-#endif
 }
 
-// layer L (1 = colour head ... 6 = sigma trunk 0) uses maxima slot (L - 1) & 1
-__device__ __forceinline__ void pc_producer_round(const float* W, float* st, uint32_t* smax,
-                                                  const float* __restrict__ h0, const float* __restrict__ sh,
-                                                  const float* __restrict__ out, const float* __restrict__ gout,
-                                                  int64_t m, bool ok, int w, int lane, float* __restrict__ gh0,
-                                                  X0Raw& X0n, int64_t mn, bool okn) {
+// X0n holds this round's h0 tile (loaded during the previous round) and leaves holding the next round's (sample
+// mn, okn); the SH row and the output / output-gradient vectors are issued behind the forward's first layer and
+// consumed after its later ones
+__device__ __forceinline__ void pc_producer_round(const float* W, float* st, const float* __restrict__ h0,
+                                                  const float* __restrict__ sh, const float* __restrict__ out,
+                                                  const float* __restrict__ gout, int64_t m, bool ok, int w,
+                                                  int lane, float* __restrict__ gh0, X0Raw& X0n, int64_t mn,
+                                                  bool okn) {
     const int h = lane >> 5;
-    uint32_t* s0 = smax;
-    uint32_t* s1 = smax + 8;
     f32x16 A1[2], A2[2], Hd[1], Cin[1], C1[2], C2[2], Rg[1];
-#if ACN_DW_PREFETCH
-    // X0n holds this round's h0 tile (loaded during the previous round); the SH row and the output / output-
-    // gradient vectors are issued before the forward recompute and consumed after its first layers
     PcIn in;
-#endif
-#if ACN_DIAG_NOPROD  // diagnostic build only: no forward recompute (zero activations): the consumers' time
-    A1[0] = A1[1] = A2[0] = A2[1] = Hd[0] = Cin[0] = C1[0] = C1[1] = C2[0] = C2[1] = Rg[0] = 0.0f;
-    (void)sh;
-#elif ACN_DW_PREFETCH
     tile_forward_x(W, X0n, sh, out, gout, m, ok, lane, in, A1, A2, Hd, Cin, C1, C2, Rg);
     __builtin_amdgcn_sched_barrier(0);
-#else
-    {
-        f32x16 X0[1];
-        tile_forward(W, h0, sh, m, ok, lane, X0, A1, A2, Hd, Cin, C1, C2, Rg);
-    }
-#endif
     f32x16 dRg[1], dHd[1];
     dRg[0] = 0.0f;
     float dsig = 0.0f;
-#if ACN_DW_PREFETCH
     {   // selects, not a branch: a branch would let the compiler sink the prefetched loads into it
         const bool rgb = ok && h == 0, sg = ok && h != 0;
         float gv[3], ov[3];
@@ -1656,117 +1077,81 @@ __device__ __forceinline__ void pc_producer_round(const float* W, float* st, uin
         for (int c = 0; c < 3; ++c) dRg[0][c] = rgb ? grad_rgb(gv[c], ov[c]) : 0.0f;
         dsig = sg ? grad_sigma(gv[0], ov[0]) : 0.0f;
     }
-#else
-    if (ok) {
-        if (h == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float y = out[m * 4 + c];
-                dRg[0][c] = grad_rgb(gout[m * 4 + c], y);
-            }
-        } else {
-            dsig = grad_sigma(gout[m * 4 + 3], out[m * 4 + 3]);
-        }
-    }
-#endif
     // colour head
-    if (kPcScaled) {
-        pc_publish<1, 2>(s0, dRg, C2, w, lane);
-        pc_sync();
-    }
-    if (ACN_DW_HEADSYNC) pc_sync();   // the consumers have finished the previous round's last layer: stage free
-    pc_put<1, 2>(st, dRg, C2, s0, w, lane);
-    pc_sync();
+    __syncthreads();   // the consumers have finished the previous round's last layer: stage free
+    pc_put<1, 2>(st, dRg, C2, w, lane);
+    __syncthreads();
     f32x16 G2[2], G1[2], Gc[1];
-    PC_BWD(bwd_layer<2, 1, 3, 32>(W + L_WC2, S64, dRg, G2, lane));
+    bwd_layer<2, 1, 3, 32>(W + L_WC2, S64, dRg, G2, lane);
     relu_mask<2>(G2, C2);
-    pc_publish<2, 2>(s1, G2, C1, w, lane);
-    pc_sync();
+    __syncthreads();
     // colour layer 1
-    pc_put<2, 2>(st, G2, C1, s1, w, lane);
-    pc_sync();
-    PC_BWD(bwd_layer<2, 2, 64, 64>(W + L_WC1, S64, G2, G1, lane));
+    pc_put<2, 2>(st, G2, C1, w, lane);
+    __syncthreads();
+    bwd_layer<2, 2, 64, 64>(W + L_WC1, S64, G2, G1, lane);
     relu_mask<2>(G1, C1);
-    pc_publish<2, 1>(s0, G1, Cin, w, lane);
-    pc_sync();
+    __syncthreads();
     // colour layer 0
-    pc_put<2, 1>(st, G1, Cin, s0, w, lane);
-    pc_sync();
-    PC_BWD(bwd_layer<1, 2, 64, 64>(W + L_WC0, S32, G1, Gc, lane));
+    pc_put<2, 1>(st, G1, Cin, w, lane);
+    __syncthreads();
+    bwd_layer<1, 2, 64, 64>(W + L_WC0, S32, G1, Gc, lane);  // d cin: rows 0..14 = d geo (SH rows dropped)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int f = rho(r, h);
         dHd[0][r] = f < 15 ? Gc[0][r] : (f == 15 ? dsig : 0.0f);
     }
-    pc_publish<1, 2>(s1, dHd, A2, w, lane);
-    pc_sync();
+    __syncthreads();
     // heads
-    pc_put<1, 2>(st, dHd, A2, s1, w, lane);
-    pc_sync();
+    pc_put<1, 2>(st, dHd, A2, w, lane);
+    __syncthreads();
     f32x16 GA2[2], GA1[2], GH[1];
-    PC_BWD(bwd_layer<2, 1, 16, 32>(W + L_WH, S64, dHd, GA2, lane));
+    bwd_layer<2, 1, 16, 32>(W + L_WH, S64, dHd, GA2, lane);
     relu_mask<2>(GA2, A2);
-    pc_publish<2, 2>(s0, GA2, A1, w, lane);
-    pc_sync();
+    __syncthreads();
     // sigma trunk 1
-    pc_put<2, 2>(st, GA2, A1, s0, w, lane);
-    pc_sync();
+    pc_put<2, 2>(st, GA2, A1, w, lane);
+    __syncthreads();
     f32x16 X0[1];
-#if ACN_DW_PREFETCH
     X0Raw x0c;
     load_x0raw(h0, m, ok, h, x0c);   // reloaded (L2-hot) for the last layer, issued before this layer's dX
     __builtin_amdgcn_sched_barrier(0);
-#endif
-    PC_BWD(bwd_layer<2, 2, 64, 64>(W + L_W1, S64, GA2, GA1, lane));
+    bwd_layer<2, 2, 64, 64>(W + L_W1, S64, GA2, GA1, lane);
     relu_mask<2>(GA1, A1);
-#if ACN_DW_PREFETCH
     __builtin_amdgcn_sched_barrier(0);
     x0_tile(x0c, ok, X0);
-#else
-    load_tiles<1>(h0, 32, 0, 32, m, ok, h, X0);
-#endif
-    pc_publish<2, 1>(s1, GA1, X0, w, lane);
-    pc_sync();
+    __syncthreads();
     // sigma trunk 0
-    pc_put<2, 1>(st, GA1, X0, s1, w, lane);
-    pc_sync();
-#if ACN_DW_PREFETCH
+    pc_put<2, 1>(st, GA1, X0, w, lane);
+    __syncthreads();
     load_x0raw(h0, mn, okn, h, X0n);   // the next round's h0 tile, behind dL/dh0 and the consumers' last layer
     __builtin_amdgcn_sched_barrier(0);
-#else
-    (void)X0n; (void)mn; (void)okn;
-#endif
     if (gh0) {   // overlaps the consumers' last layer (and the next round's forward recompute follows)
-        PC_BWD(bwd_layer<1, 2, 64, 64>(W + L_W0, S32, GA1, GH, lane));
+        bwd_layer<1, 2, 64, 64>(W + L_W0, S32, GA1, GH, lane);
         store_tiles<1>(gh0, 32, 0, 32, m, ok, h, GH);
     }
-    if (!ACN_DW_HEADSYNC) pc_sync();
 }
 
-template <bool PIPE = (ACN_DW_PIPE != 0)>
-__device__ __forceinline__ void pc_consumer_round(const float* st, const uint32_t* smax, int w, int lane, DwAcc& a) {
-    const uint32_t* s0 = smax;
-    const uint32_t* s1 = smax + 8;
-    if (kPcScaled) pc_sync();
-    if (ACN_DW_HEADSYNC) pc_sync();   // stage free (the producers' round-head barrier)
-    pc_sync();
-    dw_blocks<1, PIPE>(st, 0, X_ROW + 16 * w, a.aWC2, a.bWC2, pc_scale(s0), lane);
-    pc_sync();
-    pc_sync();
-    dw_blocks<4, PIPE>(st, 16 * w, X_ROW, a.aWC1, a.bWC1, pc_scale(s1), lane);
-    pc_sync();
-    pc_sync();
-    dw_blocks<2, PIPE>(st, 16 * w, X_ROW, a.aWC0, a.bWC0, pc_scale(s0), lane);
-    pc_sync();
-    pc_sync();
-    dw_blocks<1, PIPE>(st, 0, X_ROW + 16 * w, a.aHD, a.bHD, pc_scale(s1), lane);
-    pc_sync();
-    pc_sync();
-    dw_blocks<4, PIPE>(st, 16 * w, X_ROW, a.aW1, a.bW1, pc_scale(s0), lane);
-    pc_sync();
-    pc_sync();
-    dw_blocks<2, PIPE>(st, 16 * w, X_ROW, a.aW0, a.bW0, pc_scale(s1), lane);
-    if (!ACN_DW_HEADSYNC) pc_sync();
+// PIPE: the software-pipelined contraction of the fp32 stage (dw_blocks)
+template <bool PIPE>
+__device__ __forceinline__ void pc_consumer_round(const float* st, int w, int lane, DwAcc& a) {
+    __syncthreads();   // stage free (the producers' round-head barrier)
+    __syncthreads();
+    dw_blocks<1, PIPE>(st, 0, X_ROW + 16 * w, a.aWC2, a.bWC2, lane);
+    __syncthreads();
+    __syncthreads();
+    dw_blocks<4, PIPE>(st, 16 * w, X_ROW, a.aWC1, a.bWC1, lane);
+    __syncthreads();
+    __syncthreads();
+    dw_blocks<2, PIPE>(st, 16 * w, X_ROW, a.aWC0, a.bWC0, lane);
+    __syncthreads();
+    __syncthreads();
+    dw_blocks<1, PIPE>(st, 0, X_ROW + 16 * w, a.aHD, a.bHD, lane);
+    __syncthreads();
+    __syncthreads();
+    dw_blocks<4, PIPE>(st, 16 * w, X_ROW, a.aW1, a.bW1, lane);
+    __syncthreads();
+    __syncthreads();
+    dw_blocks<2, PIPE>(st, 16 * w, X_ROW, a.aW0, a.bW0, lane);
 }
 
 __global__ void __launch_bounds__(512) mlp_bwd_dw_pc_kernel(const float* __restrict__ img, const float* __restrict__ h0,
@@ -1775,78 +1160,33 @@ __global__ void __launch_bounds__(512) mlp_bwd_dw_pc_kernel(const float* __restr
                                                             float* __restrict__ gh0, float* __restrict__ partial) {
     __shared__ __attribute__((aligned(16))) float Wl[L_FLOATS];
     __shared__ __attribute__((aligned(16))) float st_base[ST_FLOATS];
-    __shared__ uint32_t pc_smax[16];   // two alternating slots of the 4 producers' max |dY|, |X| bits
     stage_weights(img, Wl);
     stage_init(st_base);   // the fp16 stage's ones row (bias sums); nothing for the fp32 stage
     __syncthreads();
     const int lane0 = threadIdx.x & 63, j = lane0 & 31;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), w = wv & 3;
     const int64_t ntiles = (M + 31) / 32;
-    // rounds are uniform over the workgroup (the same 12 -- 13 with the scaled stage -- barriers per round in
-    // both roles)
+    // rounds are uniform over the workgroup (the same 12 barriers per round in both roles): tiles past the end
+    // have zero gradients
     if (wv < 4) {
-        if (ACN_DW_PRIO == 1) __builtin_amdgcn_s_setprio(2);   // the producers' chain is the critical path
         const int64_t step = (int64_t)gridDim.x * 4;
         X0Raw X0n;
-#if ACN_DW_PREFETCH
         {
             const int64_t m0 = ((int64_t)blockIdx.x * 4 + w) * 32 + j;
             load_x0raw(h0, m0, m0 < M, lane0 >> 5, X0n);
         }
-#endif
         for (int64_t base = (int64_t)blockIdx.x * 4; base < ntiles; base += step) {
             const int64_t m = (base + w) * 32 + j, mn = m + step * 32;
-            pc_producer_round(Wl + opaque_s(0), st_base + opaque_s(0), pc_smax, h0, sh, out, gout, m, m < M, w,
+            pc_producer_round(Wl + opaque_s(0), st_base + opaque_s(0), h0, sh, out, gout, m, m < M, w,
                               opaque_v(lane0), gh0, X0n, mn, mn < M);
         }
     } else {
-        if (ACN_DW_PRIO == 2) __builtin_amdgcn_s_setprio(2);
         DwAcc a;
         dw_zero(a);
         for (int64_t base = (int64_t)blockIdx.x * 4; base < ntiles; base += (int64_t)gridDim.x * 4)
-            pc_consumer_round(st_base + opaque_s(0), pc_smax, w, opaque_v(lane0), a);
+            pc_consumer_round<true>(st_base + opaque_s(0), w, opaque_v(lane0), a);
         dw_flush(a, partial + (int64_t)blockIdx.x * NDW, w, lane0);
     }
-}
-
-// Pair-list variant (routed container): workgroup b takes the contiguous rounds [b R / G, (b+1) R / G)
-// (R = seg[K] / 128 from the device); when the expert of the next round differs, the running sums go
-// to copy (b, expert) and restart, and the new expert's image is staged.  mlp_dw_reduce_pairs_kernel
-// adds, per expert, the copies of the workgroups whose range met that expert's rounds (in b order:
-// deterministic, no atomics).  Padding slots carry zero output gradients.
-__global__ void __launch_bounds__(256) mlp_bwd_dw_pairs_kernel(const float* __restrict__ imgs,
-                                                               const float* __restrict__ h0,
-                                                               const float* __restrict__ sh,
-                                                               const float* __restrict__ out,
-                                                               const float* __restrict__ gout,
-                                                               const int64_t* __restrict__ seg, int K,
-                                                               float* __restrict__ gh0, float* __restrict__ partial) {
-    __shared__ __attribute__((aligned(16))) float Wl[L_FLOATS];
-    __shared__ __attribute__((aligned(16))) float st_base[ST_FLOATS];
-    stage_init(st_base);  // published by the staging barrier of the first round
-    const int lane0 = threadIdx.x & 63, j = lane0 & 31, w = threadIdx.x >> 6;
-    const int64_t R = seg[K] / 128, G = gridDim.x;
-    const int64_t r0 = (int64_t)blockIdx.x * R / G, r1 = ((int64_t)blockIdx.x + 1) * R / G;
-    DwAcc a;
-    dw_zero(a);
-    int cur = -1;
-    for (int64_t rd = r0; rd < r1; ++rd) {
-        const int k = seg_expert(seg, K, rd * 128);
-        if (k != cur) {
-            if (cur >= 0) {
-                dw_flush(a, partial + ((int64_t)blockIdx.x * K + cur) * NDW, w, lane0);
-                dw_zero(a);
-            }
-            __syncthreads();
-            stage_weights(imgs + (int64_t)k * L_FLOATS, Wl);
-            __syncthreads();
-            cur = k;
-        }
-        const int64_t m = (rd * 4 + w) * 32 + j;
-        DwClock dcp{};
-        dw_round(Wl + opaque_s(0), st_base + opaque_s(0), h0, sh, out, gout, m, true, w, opaque_v(lane0), gh0, a, dcp);
-    }
-    if (cur >= 0) dw_flush(a, partial + ((int64_t)blockIdx.x * K + cur) * NDW, w, lane0);
 }
 
 // dw[e] = sum over the nblk partial copies: a block sums 32 consecutive elements, its 8 thread rows
@@ -1908,16 +1248,14 @@ __global__ void __launch_bounds__(256) mlp_fwd_pairs_kernel(const float* __restr
     }
 }
 
-// Producer / consumer form of the pair-list backward (the routed container's C5 step): mlp_bwd_dw_pc_kernel's
-// roles, barriers and prefetch over mlp_bwd_dw_pairs_kernel's contiguous round range per workgroup.  When the
-// expert of the next round differs, both roles pass two barriers around the restaging of that expert's image
-// (the consumers first write their running sums to copy (b, expert) and restart), so the barrier sequence
-// stays the same in both roles.  Same owners, same stage, same k order as dw_round: bitwise the outputs of
-// mlp_bwd_dw_pairs_kernel.
-#ifndef ACN_DW_PAIRS_PC
-#define ACN_DW_PAIRS_PC 1   // 0: mlp_bwd_dw_pairs_kernel (one role per wave)
-#endif
-#if ACN_DW_PAIRS_PC
+// The pair-list backward (the routed container's C5 step): mlp_bwd_dw_pc_kernel's roles, barriers and prefetch
+// over a contiguous range of rounds per workgroup.  Workgroup b takes the rounds [b R / G, (b+1) R / G) (R =
+// seg[K] / 128 from the device, G workgroups); a round is 128 slots of one expert, and padding slots carry zero
+// output gradients.  When the expert of the next round differs, both roles pass two barriers around the
+// restaging of that expert's image (the consumers first write their running sums to copy (b, expert) and
+// restart), so the barrier sequence stays the same in both roles.  Same owners, same stage layout and same k
+// order as the single-expert kernel; mlp_dw_reduce_pairs_kernel adds, per expert, the copies of the workgroups
+// whose range met that expert's rounds, in b order: deterministic, no atomics.
 __global__ void __launch_bounds__(512) mlp_bwd_dw_pairs_pc_kernel(const float* __restrict__ imgs,
                                                                   const float* __restrict__ h0,
                                                                   const float* __restrict__ sh,
@@ -1927,7 +1265,6 @@ __global__ void __launch_bounds__(512) mlp_bwd_dw_pairs_pc_kernel(const float* _
                                                                   float* __restrict__ gh0, float* __restrict__ partial) {
     __shared__ __attribute__((aligned(16))) float Wl[L_FLOATS];
     __shared__ __attribute__((aligned(16))) float st_base[ST_FLOATS];
-    __shared__ uint32_t pc_smax[16];
     stage_init(st_base);   // published by the staging barriers of the first round
     const int lane0 = threadIdx.x & 63, j = lane0 & 31;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), w = wv & 3;
@@ -1939,9 +1276,7 @@ __global__ void __launch_bounds__(512) mlp_bwd_dw_pairs_pc_kernel(const float* _
     int64_t rd = r0;
     if (wv < 4) {
         X0Raw X0n;
-#if ACN_DW_PREFETCH
         if (r0 < r1) load_x0raw(h0, (r0 * 4 + w) * 32 + j, true, lane0 >> 5, X0n);
-#endif
         while (rd < r1) {
             const int k = seg_expert(seg, K, rd * 128);
             __syncthreads();
@@ -1949,7 +1284,7 @@ __global__ void __launch_bounds__(512) mlp_bwd_dw_pairs_pc_kernel(const float* _
             __syncthreads();
             for (; rd < r1 && seg_expert(seg, K, rd * 128) == k; ++rd) {
                 const int64_t m = (rd * 4 + w) * 32 + j, mn = m + 128;
-                pc_producer_round(Wl + opaque_s(0), st_base + opaque_s(0), pc_smax, h0, sh, out, gout, m, true, w,
+                pc_producer_round(Wl + opaque_s(0), st_base + opaque_s(0), h0, sh, out, gout, m, true, w,
                                   opaque_v(lane0), gh0, X0n, mn, rd + 1 < r1);
             }
         }
@@ -1964,12 +1299,11 @@ __global__ void __launch_bounds__(512) mlp_bwd_dw_pairs_pc_kernel(const float* _
             for (; rd < r1 && seg_expert(seg, K, rd * 128) == k; ++rd)
                 // the unpipelined contraction: the pipelined one's register allocation here leaves a 6-state
                 // WAR-on-C gap under tests/test_hazard_audit.py's margin
-                pc_consumer_round<false>(st_base + opaque_s(0), pc_smax, w, opaque_v(lane0), a);
+                pc_consumer_round<false>(st_base + opaque_s(0), w, opaque_v(lane0), a);
             dw_flush(a, partial + ((int64_t)blockIdx.x * K + k) * NDW, w, lane0);
         }
     }
 }
-#endif
 
 // dw[k][e] = sum over the workgroups b whose round range [b R / G, (b+1) R / G) met expert k's rounds of
 // copy (b, k); zero for an expert without pairs.  grid (NDW / 32, K)
@@ -2013,7 +1347,7 @@ __global__ void __launch_bounds__(256) mlp_dw_reduce_pairs_kernel(const float* _
 // [sigmoid(color_mlp(cat(geo, sh))), trunc_exp(sigma_head)] (MetaNGP.forward, models/inr/meta_ngp.py:226-241, the
 // torch.cat of :207-211 included).  One wave per 32-sample tile re-runs the forward (the tile_forward of
 // mlp_fwd_kernel, so the activations are the forward's bit for bit) and then the dX chain of mlp_bwd_kernel /
-// dw_round with the ReLU masks taken from the live activations; rows 15..30 of d cin, which those kernels drop,
+// pc_producer_round with the ReLU masks taken from the live activations; rows 15..30 of d cin, which those kernels drop,
 // are the SH gradient.  Nothing is staged, reduced or saved: after the weight staging there is no barrier, no
 // LDS write, no atomic, and every output row depends on its own sample only.
 __global__ void __launch_bounds__(256) mlp_bwd_input_kernel(const float* __restrict__ img, const float* __restrict__ h0,
@@ -2123,11 +1457,9 @@ __device__ __forceinline__ float sg_issue(__amdgpu_buffer_rsrc_t rs, const Sigma
     return r;
 }
 
-#ifndef ACN_SG_WAVES
-#define ACN_SG_WAVES 2   // waves per SIMD the register budget is held to: two 4-wave blocks (72 KB weight image each) per CU
-#endif
+constexpr int SG_WAVES = 2;   // waves per SIMD the register budget is held to: two 4-wave blocks (72 KB weight image each) per CU
 template <int INTERP>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACN_SG_WAVES, ACN_SG_WAVES)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SG_WAVES, SG_WAVES)))
 field_sigma_grad_kernel(const float* __restrict__ img, SigmaGradArgs a) {
     __shared__ __attribute__((aligned(16))) float Wl[L_FLOATS];
     stage_weights(img, Wl);
@@ -2312,12 +1644,6 @@ extern "C" int ACN_MLP_API(acn_mlp_train_bwd)(const float* save, const float* ou
     return acn_check_launch("acn_mlp_train_bwd");
 }
 
-#if ACN_DW_DIAG
-extern "C" int ACN_MLP_API(acn_mlp_dw_diag)(unsigned long long* host, int nblk) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_dw_diag), (size_t)nblk * 4 * 8 * sizeof(unsigned long long));
-}
-#endif
-
 extern "C" size_t ACN_MLP_API(acn_mlp_dw_workspace_bytes)(void) {
     return ((size_t)L_FLOATS + (size_t)MAX_DW_BLOCKS * NDW) * sizeof(float);
 }
@@ -2328,11 +1654,7 @@ int bwd_dw_launch(const float* h0, const float* sh, const float* out, const floa
                   float* dw, float* gh0, float* partial, hipStream_t s) {
     const int64_t tiles = (M + 31) / 32, want = (tiles + 3) / 4;
     const int nblk = (int)(want < MAX_DW_BLOCKS ? want : MAX_DW_BLOCKS);
-#if ACN_DW_PC
     hipLaunchKernelGGL(mlp_bwd_dw_pc_kernel, dim3(nblk), dim3(512), 0, s, img, h0, sh, out, gout, M, gh0, partial);
-#else
-    hipLaunchKernelGGL(mlp_bwd_dw_kernel, dim3(nblk), dim3(256), 0, s, img, h0, sh, out, gout, M, gh0, partial);
-#endif
     hipLaunchKernelGGL(mlp_dw_reduce_kernel, dim3((NDW + 31) / 32), dim3(256), 0, s, (const float*)partial, nblk,
                        dw);
     return acn_check_launch("acn_mlp_train_bwd_dw");
@@ -2470,13 +1792,8 @@ extern "C" int ACN_MLP_API(acn_mlp_train_bwd_dw_pairs)(const float* h0, const fl
     const float* imgs = (const float*)workspace;
     float* partial = (float*)workspace + (size_t)K * L_FLOATS;
     hipStream_t s = (hipStream_t)stream;
-#if ACN_DW_PAIRS_PC
     hipLaunchKernelGGL(mlp_bwd_dw_pairs_pc_kernel, dim3(PAIR_DW_BLOCKS), dim3(512), 0, s, imgs, h0, sh, out, gout, seg, K,
                        gh0, partial);
-#else
-    hipLaunchKernelGGL(mlp_bwd_dw_pairs_kernel, dim3(PAIR_DW_BLOCKS), dim3(256), 0, s, imgs, h0, sh, out, gout, seg, K,
-                       gh0, partial);
-#endif
     hipLaunchKernelGGL(mlp_dw_reduce_pairs_kernel, dim3((NDW + 31) / 32, K), dim3(256), 0, s, (const float*)partial,
                        seg, K, PAIR_DW_BLOCKS, dw);
     return acn_check_launch("acn_mlp_train_bwd_dw_pairs");

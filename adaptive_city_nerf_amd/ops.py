@@ -773,7 +773,7 @@ def mlp_fn(name: str, precision: Optional[str] = None):
     return getattr(_lib.lib(), name + _MLP_SUFFIX[precision or TRAIN_MLP_PRECISION])
 # Optional timing hook (bench.py --workload meta): when set to a list, every acn_mlp_train_bwd_dw call appends
 # (start event, end event, M, want_h0) recorded on the current stream around the call (weight pack +
-# mlp_bwd_dw_kernel + mlp_dw_reduce_kernel)
+# mlp_bwd_dw_pc_kernel + mlp_dw_reduce_kernel)
 DW_HOOK = None
 # Algorithmic MACs per sample of the fused MLP backward (SURVEY §8(d) MLP shapes): dW = every weight
 # (32x64 + 64x64 + 64x[15|1] + 31x64 + 64x64 + 64x3 = 13,440); dX = the layer-input gradients the chain

@@ -1,8 +1,7 @@
-"""Which role bounds the producer / consumer MLP backward (developer tool): acn_mlp_train_bwd_dw at
-the meta batch (362,666 samples, the meta step's average launch) for the default fp16x3 and the use_amp kernels,
-on whatever libacnerf.so ACNERF_LIB names -- the regular build, or the diagnostic builds without the
-weight-gradient contraction (ACN_DIAG_NODW: the producers' time) or without the producers' forward recompute and
-dX chain (ACN_DIAG_NOPROD: the consumers' time)."""
+"""Time of the producer / consumer MLP backward (developer tool): acn_mlp_train_bwd_dw at the meta batch (362,666
+samples, the meta step's average launch) for the default fp16x3 and the use_amp kernels, on whatever libacnerf.so
+ACNERF_LIB names (the regular build by default).  The per-role figures of docs/DESIGN_HISTORY.md 4i came from
+this driver on two diagnostic builds that have since been retired."""
 import sys
 import torch
 
