@@ -173,6 +173,8 @@ SIGNATURES = {
     "acn_normal_composite": ([vp, vp, i64, i32, vp, vp], C.c_int),
     "acn_distortion_packed": ([vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp], C.c_int),
     "acn_distortion_dense": ([vp, vp, i64, i32, vp, vp, vp, vp], C.c_int),
+    "acn_depth_loss_packed": ([vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp], C.c_int),
+    "acn_depth_loss_dense": ([vp, vp, i64, i32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp], C.c_int),
     # resample.hip
     "acn_resample_pdf": ([vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp], C.c_int),
     # interlevel.hip

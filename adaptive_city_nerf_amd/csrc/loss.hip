@@ -9,7 +9,8 @@
 // the float exponent, clamps that pass NaN through, and mse_loss_backward's double `2 / numel` factor.
 // Also here, as the other small per-ray reduction: acn_normal_composite, the weighted sum of the samples' unit
 // normals of a rendered normal map, and the distortion regulariser of the weights along a ray with its
-// gradient (acn_distortion_packed / acn_distortion_dense).
+// gradient (acn_distortion_packed / acn_distortion_dense), and depth supervision in the same form
+// (acn_depth_loss_packed / acn_depth_loss_dense).
 #include "acn_device.h"
 #include "acn_internal.h"
 
@@ -255,7 +256,141 @@ int launch_distortion(const DistortionArgs& a, void* stream, const char* what) {
     return acn_check_launch(what);
 }
 
+// Depth supervision (acn_depth_loss_packed / acn_depth_loss_dense): for one ray with weights w_i over
+// the intervals [s_i, e_i], per-sample depths tau_i, a target depth z, a half-width eps and a length scale c,
+//   sigma = eps / 3, lo = z - eps, hi = z + eps, Phi the standard normal CDF
+//   k_i      = Phi((min(e_i, hi) - z) / sigma) - Phi((max(s_i, lo) - z) / sigma) if min(e_i, hi) > max(s_i, lo), else 0
+//   m_i      = 1 if s_i < hi else 0
+//   D        = sum_i w_i tau_i
+//   L        = l_d (c (D - z))^2 + l_s sum_i m_i (w_i - k_i)^2
+//   dL/dw_i  = 2 l_d c^2 (D - z) tau_i + 2 l_s m_i (w_i - k_i)
+// (the expected-depth term of DS-NeRF and the line-of-sight term of Urban Radiance Fields: k is the mass a Gaussian of
+// deviation eps / 3 cut at +-eps puts into interval i; samples in front of the window pay w^2, samples behind it
+// nothing).  The shape of distortion_kernel: one wave per ray, 64 samples per step; pass 1 sums w tau over the ray,
+// pass 2 computes the terms and the gradient.  Everything from the fp32 inputs on is double (z +- eps, the clipping
+// and the comparisons are exact there, Phi through erf) and each output is rounded to fp32 once.  No atomics, no LDS:
+// bitwise reproducible.  A ray without a target (z or eps not finite or <= 0) or with c exactly 0 gets zeros, and its
+// t values are not read.
+// DENSE: s_i = tau_i = t_i, e_i = t_i + d_i with volume_render's dists (distortion_interval<true>'s d).  Packed:
+// s = t0, e = t1, tau = (t0 + t1) / 2 of samples starts[r] .. + counts[r], cut at M.
+struct DepthLossArgs {
+    DistortionArgs d;                // w, t0, t1, starts, counts, M, N, S, ray_scale, loss, grad_w
+    const float *depth, *eps;        // (N)
+    double depth_weight, sight_weight;
+};
+
+__device__ __forceinline__ double normal_cdf(double x) { return 0.5 * (1.0 + erf(x * 0.70710678118654752440)); }
+
+// start, end and depth of sample k (< n) of the ray whose first sample is b
+template <bool DENSE>
+__device__ __forceinline__ void depth_sample(const DistortionArgs& a, int64_t b, int64_t k, int64_t n, double& s,
+                                             double& e, double& tau) {
+    if (DENSE) {
+        double m, d;
+        distortion_interval<true>(a, b, k, n, m, d);
+        s = (double)a.t0[b + k];
+        e = s + d;
+        tau = s;
+    } else {
+        s = (double)a.t0[b + k];
+        e = (double)a.t1[b + k];
+        tau = 0.5 * (s + e);
+    }
+}
+
+template <bool DENSE>
+__global__ void __launch_bounds__(256) depth_loss_kernel(DepthLossArgs p) {
+    const DistortionArgs& a = p.d;
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < a.N; r += nw) {
+        int64_t b, n;
+        if (DENSE) {
+            b = r * a.S;
+            n = a.S;
+        } else {
+            b = a.starts[r];
+            n = a.counts[r];
+            if (b < 0 || b > a.M || n < 0) n = 0;   // a range outside the samples is empty, one past M is cut
+            if (n > a.M - b) n = a.M - b;
+        }
+        const double c = a.ray_scale ? (double)a.ray_scale[r] : 1.0;
+        const float zf = p.depth[r], ef = p.eps[r];
+        // wave-uniform: zeros, and the ray's t values (NaN for an invalid ray) are not read
+        if (!(isfinite(zf) && zf > 0.0f && isfinite(ef) && ef > 0.0f) || c == 0.0) {
+            if (a.grad_w)
+                for (int64_t k = lane; k < n; k += 64) a.grad_w[b + k] = 0.0f;
+            if (lane == 0) a.loss[r] = 0.0f;
+            continue;
+        }
+        const double z = (double)zf, eps = (double)ef;
+        const double lo = z - eps, hi = z + eps, sigma = eps / 3.0;
+        double wtau = 0.0;   // this lane's share of D
+        for (int64_t k = lane; k < n; k += 64) {
+            double s, e, tau;
+            depth_sample<DENSE>(a, b, k, n, s, e, tau);
+            wtau += (double)a.w[b + k] * tau;
+        }
+        const double diff = acn::wave_sum_d(wtau) - z;   // D - z
+        const double gd = 2.0 * p.depth_weight * c * c * diff;
+        double acc = 0.0;   // this lane's share of the sight term
+        for (int64_t k = lane; k < n; k += 64) {
+            double s, e, tau;
+            depth_sample<DENSE>(a, b, k, n, s, e, tau);
+            const double w = (double)a.w[b + k];
+            const double x0 = s > lo ? s : lo, x1 = e < hi ? e : hi;   // the interval clipped to the window
+            double kk = 0.0;
+            if (x1 > x0) kk = normal_cdf((x1 - z) / sigma) - normal_cdf((x0 - z) / sigma);
+            const double u = s < hi ? w - kk : 0.0;
+            acc += u * u;
+            if (a.grad_w) a.grad_w[b + k] = (float)(gd * tau + 2.0 * p.sight_weight * u);
+        }
+        acc = acn::wave_sum_d(acc);
+        const double cd = c * diff;
+        if (lane == 0) a.loss[r] = (float)(p.depth_weight * (cd * cd) + p.sight_weight * acc);
+    }
+}
+
+template <bool DENSE>
+int launch_depth_loss(const DepthLossArgs& p, void* stream, const char* what) {
+    const int64_t wgs = (p.d.N + 3) / 4;   // 4 waves (rays) per 256-thread workgroup, grid-stride past 4096 of them
+    hipLaunchKernelGGL(depth_loss_kernel<DENSE>, dim3((unsigned)(wgs < 4096 ? wgs : 4096)), dim3(256), 0,
+                       (hipStream_t)stream, p);
+    return acn_check_launch(what);
+}
+
 }  // namespace
+
+extern "C" int acn_depth_loss_packed(const float* weights, const float* t_starts, const float* t_ends, int64_t M,
+                                     const int64_t* chunk_starts, const int64_t* chunk_cnts, int64_t N,
+                                     const float* depth, const float* eps, const float* ray_scale, double depth_weight,
+                                     double sight_weight, float* loss, float* grad_w, void* stream) {
+    ACN_REQUIRE(N >= 0 && M >= 0, "acn_depth_loss_packed: N and M must be >= 0 (got %lld, %lld)", (long long)N,
+                (long long)M);
+    ACN_REQUIRE(depth_weight >= 0.0 && sight_weight >= 0.0,
+                "acn_depth_loss_packed: depth_weight and sight_weight must be >= 0 (got %g, %g)", depth_weight,
+                sight_weight);
+    if (N == 0) return ACN_OK;
+    ACN_REQUIRE(chunk_starts && chunk_cnts && depth && eps && loss, "acn_depth_loss_packed: NULL pointer");
+    ACN_REQUIRE(M == 0 || (weights && t_starts && t_ends), "acn_depth_loss_packed: NULL sample array");
+    DepthLossArgs p{{weights, t_starts, t_ends, chunk_starts, chunk_cnts, M, N, 0, ray_scale, loss, grad_w},
+                    depth, eps, depth_weight, sight_weight};
+    return launch_depth_loss<false>(p, stream, "acn_depth_loss_packed");
+}
+
+extern "C" int acn_depth_loss_dense(const float* weights, const float* t_vals, int64_t N, int S, const float* depth,
+                                    const float* eps, const float* ray_scale, double depth_weight, double sight_weight,
+                                    float* loss, float* grad_w, void* stream) {
+    ACN_REQUIRE(N >= 0 && S >= 2, "acn_depth_loss_dense: N must be >= 0 and S >= 2 (got %lld, %d)", (long long)N, S);
+    ACN_REQUIRE(depth_weight >= 0.0 && sight_weight >= 0.0,
+                "acn_depth_loss_dense: depth_weight and sight_weight must be >= 0 (got %g, %g)", depth_weight,
+                sight_weight);
+    if (N == 0) return ACN_OK;
+    ACN_REQUIRE(weights && t_vals && depth && eps && loss, "acn_depth_loss_dense: NULL pointer");
+    DepthLossArgs p{{weights, t_vals, nullptr, nullptr, nullptr, N * (int64_t)S, N, S, ray_scale, loss, grad_w},
+                    depth, eps, depth_weight, sight_weight};
+    return launch_depth_loss<true>(p, stream, "acn_depth_loss_dense");
+}
 
 extern "C" int acn_distortion_packed(const float* weights, const float* t_starts, const float* t_ends, int64_t M,
                                      const int64_t* chunk_starts, const int64_t* chunk_cnts, int64_t N,

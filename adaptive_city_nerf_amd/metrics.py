@@ -15,6 +15,8 @@ layout and return values, so the reference's call reads unchanged:
 * ``ssim_image``: the same metric on ``(H, W, C)`` frames, the layout ``render_image`` returns, read in place.
 * ``image_metrics`` / ``evaluate_image``: PSNR (``parallel.psnr_reduce``'s formula) and SSIM of a frame in one of the
   reference's colour spaces; render plus metrics in one call.
+* ``depth_metrics``: the absolute relative error and the RMSE of a rendered depth against the entries of a target that
+  carry a depth (what depth-supervised training, DESIGN.md §4ab, is read against).
 
 One deviation, on purpose: a spatial dimension smaller than ``win_size`` raises ``AcnError``; pytorch_msssim warns and
 skips the filter along that dimension.  MS-SSIM, a caller-supplied window, the 3-D (video) form and LPIPS (which needs
@@ -36,7 +38,7 @@ from . import ops
 from ._lib import AcnError
 from .color_space import color_space_transformer
 
-__all__ = ["ssim", "ssim_image", "image_metrics", "evaluate_image"]
+__all__ = ["ssim", "ssim_image", "image_metrics", "evaluate_image", "depth_metrics"]
 
 
 def _gauss_window(win_size: int, win_sigma: float, device) -> Tensor:
@@ -155,6 +157,22 @@ def image_metrics(pred_lin: Tensor, gt_srgb: Tensor, metrics_space: str = "linea
     d = p.double() - g.double()
     mse = max(float((d * d).sum()) / max(float(d.numel()), 1.0), 1e-8)
     return {"psnr": -10.0 * math.log10(mse), "ssim": float(ssim_image(p, g, data_range=1.0))}
+
+
+def depth_metrics(pred: Tensor, gt: Tensor) -> Dict[str, float]:
+    """{"abs_rel", "rmse"} of a rendered depth against a target of the same shape, over the entries where ``gt`` is
+    finite and > 0 (NaN marks a pixel without a target, as ray_sampling.point_depth_targets writes it): abs_rel =
+    mean |pred - gt| / gt, rmse = sqrt(mean (pred - gt)^2), in float64.  Without any such entry both are NaN."""
+    if pred.shape != gt.shape:
+        raise AcnError(f"depth_metrics: pred and gt must share one shape, got {tuple(pred.shape)} and "
+                       f"{tuple(gt.shape)}")
+    g = gt.detach().double().reshape(-1)
+    p = pred.detach().to(g.device).double().reshape(-1)
+    keep = torch.isfinite(g) & (g > 0)
+    if not bool(keep.any()):
+        return {"abs_rel": float("nan"), "rmse": float("nan")}
+    d, g = p[keep] - g[keep], g[keep]
+    return {"abs_rel": float((d.abs() / g).mean()), "rmse": math.sqrt(float((d * d).mean()))}
 
 
 @torch.no_grad()

@@ -18,6 +18,8 @@ read unchanged:
   HIP backward kernels behind autograd Functions.
 * ``distortion`` (``nerfacc.losses.distortion``): the mip-NeRF 360 regulariser of the weights along each ray,
   loss and gradient from one HIP launch.
+* ``depth_loss`` (an extension, not in nerfacc): depth supervision of the weights along each ray, an expected-depth
+  term plus a line-of-sight term, loss and gradient from one HIP launch.
 
 Parity with nerfacc itself is UNPINNED (no nerfacc code or fixture exists in this environment); the
 kernels are checked bit for bit (traversal) / within tolerance (compositing) against the oracle's
@@ -37,7 +39,7 @@ from ._lib import AcnError
 
 __all__ = ["OccGridEstimator", "ray_aabb_intersect", "traverse_grids", "pack_info",
            "render_transmittance_from_density", "render_weight_from_density", "render_visibility_from_density",
-           "accumulate_along_rays", "distortion"]
+           "accumulate_along_rays", "distortion", "depth_loss"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -259,6 +261,163 @@ def distortion(weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: O
     ri = ray_indices.long() if ray_indices is not None else None
     return _DistortionFn.apply(weights, t0, t1, starts, counts, ri, None,
                                torch.is_grad_enabled() and weights.requires_grad)
+
+
+# ----------------------------------------------------------------------------------------------
+# Depth supervision (the expected-depth term of DS-NeRF and the line-of-sight term of Urban Radiance
+# Fields): per ray with target z, half-width eps, sigma = eps / 3, window [lo, hi] = [z - eps, z + eps], scale c,
+#   k_i = Phi((min(e_i, hi) - z) / sigma) - Phi((max(s_i, lo) - z) / sigma) where that range is not empty, else 0
+#   L   = l_d (c (sum_i w_i tau_i - z))^2 + l_s sum_{s_i < hi} (w_i - k_i)^2
+# over the intervals [s_i, e_i] with depths tau_i; the t values, z and eps carry no gradient.
+class _DepthLossFn(torch.autograd.Function):
+    """One HIP launch (acn_depth_loss_packed / acn_depth_loss_dense) that returns the per-ray loss and keeps
+    d loss / d weights for the backward, which is g_loss[ray] * grad_w: _DistortionFn with the targets ``depths`` and
+    ``eps`` (N,) and the two weights.  ``starts`` None: the dense layout (``ta`` = t_vals (N, S)); else packed samples
+    [ta_i, tb_i] whose rays are ``ray_indices`` (M,), or equal rows of M / N samples when that is None."""
+
+    @staticmethod
+    def forward(ctx, weights, ta, tb, starts, counts, ray_indices, depths, eps, ray_scale, depth_weight, sight_weight,
+                want_grad):
+        if starts is None:
+            loss, grad = ops.depth_loss_dense(weights, ta, depths, eps, ray_scale, depth_weight, sight_weight,
+                                              want_grad=want_grad)
+        else:
+            loss, grad = occ_ops.depth_loss_packed(weights.reshape(-1), ta.reshape(-1), tb.reshape(-1), starts, counts,
+                                                   depths, eps, ray_scale, depth_weight, sight_weight,
+                                                   want_grad=want_grad)
+        ctx.set_materialize_grads(False)
+        ctx.shape = weights.shape
+        ctx.by_index = ray_indices is not None
+        if want_grad:
+            ctx.save_for_backward(grad, *((ray_indices,) if ctx.by_index else ()))
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        if g_loss is None or not ctx.needs_input_grad[0]:
+            return (None,) * 12
+        grad = ctx.saved_tensors[0]
+        if ctx.by_index:
+            g = g_loss.index_select(0, ctx.saved_tensors[1]) * grad
+        else:
+            g = (g_loss.unsqueeze(1) * grad.view(g_loss.shape[0], -1))
+        return (g.view(ctx.shape),) + (None,) * 11
+
+
+def _depth_live(depths: Tensor, eps: Tensor, ray_scale: Optional[Tensor] = None) -> Tensor:
+    """(N,) bool: the rays that carry a target (depth and eps finite and > 0, scale not 0)."""
+    live = torch.isfinite(depths) & (depths > 0) & torch.isfinite(eps) & (eps > 0)
+    return live if ray_scale is None else live & (ray_scale != 0)
+
+
+def _depth_loss_torch(weights: Tensor, s: Tensor, e: Tensor, tau: Tensor, depths: Tensor, eps: Tensor,
+                      ray_scale: Optional[Tensor] = None, depth_weight: float = 1.0, sight_weight: float = 1.0,
+                      ray_indices: Optional[Tensor] = None, n_rays: Optional[int] = None) -> Tensor:
+    """The kernels' formula as float64 torch ops (CPU tensors, other dtypes than fp32, and inside second_order():
+    differentiable any number of times in the weights).  ``s`` / ``e`` / ``tau``: float64 interval starts, ends and
+    depths, (N, S) with ``ray_indices`` None, else packed (M,) samples of ``n_rays`` rays; ``depths`` and ``eps`` (N,).
+    A ray without a target or with scale 0 gets an exact 0 whatever its t values are."""
+    z, ep = depths.detach().double(), eps.detach().double()
+    c = torch.ones_like(z) if ray_scale is None else ray_scale.detach().double()
+    live = _depth_live(z, ep, None if ray_scale is None else c)
+    one = torch.ones_like(z)
+    z, ep, c = torch.where(live, z, one), torch.where(live, ep, one), torch.where(live, c, torch.zeros_like(c))
+    per = (lambda v: v.unsqueeze(1)) if ray_indices is None else (lambda v: v.index_select(0, ray_indices))
+    keep, zz = per(live), per(z)
+    zero = torch.zeros_like(s)
+    w = torch.where(keep, weights.double(), zero)
+    s, e, tau = torch.where(keep, s, zero), torch.where(keep, e, zero), torch.where(keep, tau, zero)
+    sigma, lo, hi = per(ep) / 3.0, zz - per(ep), zz + per(ep)
+    x0, x1 = torch.maximum(s, lo), torch.minimum(e, hi)
+    cdf = lambda x: 0.5 * (1.0 + torch.special.erf(x * 0.70710678118654752440))   # noqa: E731
+    k = torch.where(x1 > x0, cdf((x1 - zz) / sigma) - cdf((x0 - zz) / sigma), zero)
+    u = torch.where(s < hi, w - k, zero)
+    if ray_indices is None:
+        D, sight = (w * tau).sum(1), (u * u).sum(1)
+    else:
+        D = z.new_zeros(int(n_rays)).index_add(0, ray_indices, w * tau)
+        sight = z.new_zeros(int(n_rays)).index_add(0, ray_indices, u * u)
+    cd = c * (D - z)
+    loss = float(depth_weight) * (cd * cd) + float(sight_weight) * sight
+    return torch.where(live, loss, torch.zeros_like(loss)).to(weights.dtype)
+
+
+def _depth_targets(depths: Tensor, eps, N: int, device, what: str) -> Tuple[Tensor, Tensor]:
+    """(depths (N,), eps (N,)) detached on ``device``; ``eps`` a float or an (N,) tensor."""
+    if depths is None or eps is None:
+        raise ValueError(f"{what}: depths and eps are required")
+    z = depths.detach().to(device).reshape(-1)
+    if z.numel() != N:
+        raise AcnError(f"{what}: depths must be ({N},), got {tuple(depths.shape)}")
+    if not z.is_floating_point():
+        z = z.float()
+    if isinstance(eps, Tensor):
+        ep = eps.detach().to(device, z.dtype).reshape(-1)
+        if ep.numel() == 1 and N != 1:
+            ep = ep.expand(N)
+        if ep.numel() != N:
+            raise AcnError(f"{what}: eps must be a float or ({N},), got {tuple(eps.shape)}")
+    else:
+        ep = torch.full((N,), float(eps), dtype=z.dtype, device=device)
+    return z, ep
+
+
+def _check_depth_weights(depth_weight, sight_weight, what: str) -> Tuple[float, float]:
+    ld, ls = float(depth_weight), float(sight_weight)
+    if not (ld >= 0.0 and ls >= 0.0):
+        raise AcnError(f"{what}: depth_weight and sight_weight must be >= 0, got {depth_weight} and {sight_weight}")
+    return ld, ls
+
+
+def depth_loss(weights: Tensor, t_starts: Tensor, t_ends: Tensor, depths: Tensor, eps,
+               ray_indices: Optional[Tensor] = None, n_rays: Optional[int] = None,
+               ray_scale: Optional[Tensor] = None, depth_weight: float = 1.0, sight_weight: float = 1.0) -> Tensor:
+    """(n_rays,) depth supervision of each ray's weights (an extension): with the target ``depths[r]``
+    = z (distance along the ray), the half-width ``eps`` (a float or (n_rays,)), sigma = eps / 3 and c =
+    ``ray_scale[r]`` (1),
+
+        depth_weight (c (sum_i w_i (t_starts_i + t_ends_i) / 2 - z))^2
+            + sight_weight sum_{t_starts_i < z + eps} (w_i - k_i)^2
+
+    k_i the mass the Gaussian N(z, sigma) cut at z +- eps puts into [t_starts_i, t_ends_i]: samples in front of the
+    window pay w^2, samples behind it nothing.  A ray whose depth or eps is not finite or <= 0 (NaN marks a ray
+    without a target), or whose scale is 0, contributes an exact 0.  Packed (M,) samples with their ``ray_indices``
+    (ray-sorted; without them the samples are one ray), or batched (n_rays, n_samples) tensors.  Differentiable in
+    ``weights`` (one fused HIP launch forward, one multiply backward); nothing else carries a gradient."""
+    if not (weights.shape == t_starts.shape == t_ends.shape) or weights.dim() not in (1, 2):
+        raise AcnError(f"depth_loss: weights, t_starts and t_ends must share one shape, (M,) or (n_rays, n_samples); "
+                       f"got {tuple(weights.shape)}, {tuple(t_starts.shape)}, {tuple(t_ends.shape)}")
+    ld, ls = _check_depth_weights(depth_weight, sight_weight, "depth_loss")
+    t0, t1 = t_starts.detach(), t_ends.detach()
+    dev = weights.device
+    want = torch.is_grad_enabled() and weights.requires_grad
+    if weights.dim() == 2:
+        if ray_indices is not None:
+            raise AcnError("depth_loss: ray_indices go with packed (M,) samples, not with (n_rays, n_samples)")
+        N, S = weights.shape
+        if n_rays is not None and int(n_rays) != N:
+            raise AcnError(f"depth_loss: n_rays = {n_rays} but weights has {N} rows")
+        z, ep = _depth_targets(depths, eps, N, dev, "depth_loss")
+        rs = None if ray_scale is None else ray_scale.detach().to(dev).reshape(-1)
+        if not _distortion_fused(weights):
+            return _depth_loss_torch(weights, t0.double(), t1.double(), 0.5 * (t0.double() + t1.double()), z, ep, rs,
+                                     ld, ls)
+        starts = torch.arange(N, dtype=torch.long, device=dev) * S
+        return _DepthLossFn.apply(weights, t0, t1, starts, torch.full_like(starts, S), None, z, ep, rs, ld, ls, want)
+    if ray_indices is not None and ray_indices.shape != weights.shape:
+        raise AcnError(f"depth_loss: ray_indices must be ({weights.shape[0]},), got {tuple(ray_indices.shape)}")
+    if n_rays is None:
+        n_rays = 1 if ray_indices is None else (int(ray_indices.max().item()) + 1 if ray_indices.numel() else 0)
+    z, ep = _depth_targets(depths, eps, int(n_rays), dev, "depth_loss")
+    rs = None if ray_scale is None else ray_scale.detach().to(dev).reshape(-1)
+    if not _distortion_fused(weights):
+        ri = torch.zeros(weights.shape[0], dtype=torch.long, device=dev) if ray_indices is None else ray_indices.long()
+        return _depth_loss_torch(weights, t0.double(), t1.double(), 0.5 * (t0.double() + t1.double()), z, ep, rs, ld,
+                                 ls, ri, int(n_rays))
+    starts, counts = _packed(None, ray_indices, int(n_rays), weights.numel(), dev)
+    ri = ray_indices.long() if ray_indices is not None else None
+    return _DepthLossFn.apply(weights, t0, t1, starts, counts, ri, z, ep, rs, ld, ls, want)
 
 
 # ----------------------------------------------------------------------------------------------

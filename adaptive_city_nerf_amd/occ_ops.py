@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import AcnError, check, ptr, require_hip, stream_of
-from .ops import _experts_array, _f32, _ray_scale_arg, pack_experts
+from .ops import _depth_target_args, _experts_array, _f32, _ray_scale_arg, pack_experts
 
 I64 = torch.int64
 # single-pass traversal: per-ray scratch rows of SINGLE_PASS_CAP samples while the scratch stays under
@@ -248,6 +248,37 @@ def distortion_packed(weights, t0, t1, starts, counts, ray_scale: Optional[torch
     grad = torch.empty(M, device=dev, dtype=torch.float32) if want_grad else None
     check(_lib.lib().acn_distortion_packed(ptr(ww), ptr(a), ptr(b), M, ptr(st), ptr(ct), N, ptr(rs), ptr(loss),
                                            ptr(grad), stream_of(ww)), "acn_distortion_packed")
+    return loss, grad
+
+
+def depth_loss_packed(weights, t0, t1, starts, counts, depths, eps, ray_scale: Optional[torch.Tensor] = None,
+                      depth_weight: float = 1.0, sight_weight: float = 1.0, want_grad: bool = True):
+    """(loss (N,), d loss / d weights (M,) or None) of the depth supervision over packed samples
+    (acn_depth_loss_packed): intervals [t0_i, t1_i] with the depths tau_i = (t0_i + t1_i) / 2 the packed
+    compositing accumulates; target z = ``depths[r]``, half-width ``eps`` (a float or (N,)), c = ``ray_scale[r]`` (1),
+    loss = depth_weight (c (sum_i w_i tau_i - z))^2 + sight_weight sum_{t0_i < z + eps} (w_i - k_i)^2 (ops.
+    depth_loss_dense).  One launch; float64 arithmetic, one fp32 rounding per output; bitwise reproducible.  An empty
+    ray has D = 0 and no gradient; a ray without a target or with scale 0 gets zeros and its t values are not read.
+    The rays' ranges partition the samples, as pack_info's do; a range reaching past M is cut at M by the kernel."""
+    if weights.dim() != 1 or t0.shape != weights.shape or t1.shape != weights.shape:
+        raise AcnError(f"depth_loss_packed: weights, t0 and t1 must be (M,), got {tuple(weights.shape)}, "
+                       f"{tuple(t0.shape)}, {tuple(t1.shape)}")
+    if starts.dim() != 1 or counts.shape != starts.shape:
+        raise AcnError(f"depth_loss_packed: starts and counts must be (N,), got {tuple(starts.shape)}, "
+                       f"{tuple(counts.shape)}")
+    require_hip(weights, "depth_loss_packed")
+    ww, a, b = _f32(weights), _f32(t0), _f32(t1)
+    st, ct = _as_i64(starts), _as_i64(counts)
+    dev = ww.device
+    if any(t.device != dev for t in (a, b, st, ct)):
+        raise AcnError("depth_loss_packed: every tensor must be on the weights' device")
+    M, N = ww.numel(), st.numel()
+    z, e, ld, ls = _depth_target_args(depths, eps, depth_weight, sight_weight, N, dev, "depth_loss_packed")
+    rs = _ray_scale_arg(ray_scale, N, dev, "depth_loss_packed")
+    loss = torch.empty(N, device=dev, dtype=torch.float32)
+    grad = torch.empty(M, device=dev, dtype=torch.float32) if want_grad else None
+    check(_lib.lib().acn_depth_loss_packed(ptr(ww), ptr(a), ptr(b), M, ptr(st), ptr(ct), N, ptr(z), ptr(e), ptr(rs), ld,
+                                           ls, ptr(loss), ptr(grad), stream_of(ww)), "acn_depth_loss_packed")
     return loss, grad
 
 

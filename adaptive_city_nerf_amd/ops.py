@@ -952,7 +952,55 @@ def distortion_dense(weights: torch.Tensor, t_vals: torch.Tensor, ray_scale: Opt
     return loss, grad
 
 
-SSIM_TILE_H = SSIM_TILE_W = 32   # ACN_SSIM_TILE: map pixels (forward) / image pixels (gradient) per workgroup
+def _depth_target_args(depths, eps, depth_weight, sight_weight, N: int, device, what: str):
+    """The (N,) fp32 targets and half-widths (``eps`` a float or an (N,) tensor) and the two weights as floats."""
+    z = _f32(depths).reshape(-1)
+    if z.numel() != N or z.device != device:
+        raise AcnError(f"{what}: depths must be ({N},) on the weights' device, got {tuple(depths.shape)} on "
+                       f"{depths.device}")
+    if isinstance(eps, torch.Tensor):
+        e = _f32(eps).reshape(-1)
+        if e.numel() == 1 and N != 1:
+            e = e.expand(N).contiguous()
+        if e.numel() != N or e.device != device:
+            raise AcnError(f"{what}: eps must be a float or ({N},) on the weights' device, got {tuple(eps.shape)} on "
+                           f"{eps.device}")
+    else:
+        e = torch.full((N,), float(eps), device=device, dtype=torch.float32)
+    ld, ls = float(depth_weight), float(sight_weight)
+    if not (ld >= 0.0 and ls >= 0.0):
+        raise AcnError(f"{what}: depth_weight and sight_weight must be >= 0, got {depth_weight} and {sight_weight}")
+    return z, e, ld, ls
+
+
+def depth_loss_dense(weights: torch.Tensor, t_vals: torch.Tensor, depths: torch.Tensor, eps,
+                     ray_scale: Optional[torch.Tensor] = None, depth_weight: float = 1.0, sight_weight: float = 1.0,
+                     want_grad: bool = True):
+    """(loss (N,), d loss / d weights (N, S) or None) of the depth supervision over the compositing's own intervals
+    (acn_depth_loss_dense): s_i = tau_i = t_i, e_i = t_i + d_i with volume_render's ``dists``; with the
+    target z = ``depths[r]``, the half-width ``eps`` (a float or (N,)), sigma = eps / 3 and c = ``ray_scale[r]`` (1),
+    k_i the mass of the Gaussian N(z, sigma) cut at z +- eps inside [s_i, e_i],
+    loss = depth_weight (c (sum_i w_i t_i - z))^2 + sight_weight sum_{s_i < z + eps} (w_i - k_i)^2.  One launch; float64
+    arithmetic, one fp32 rounding per output; bitwise reproducible.  A ray whose target or eps is not finite or <= 0,
+    or whose scale is exactly 0, gets zeros and its t values are not read."""
+    if weights.dim() != 2 or weights.shape[1] < 2 or t_vals.shape != weights.shape:
+        raise AcnError(f"depth_loss_dense: weights and t_vals must both be (N, S >= 2), got {tuple(weights.shape)} and "
+                       f"{tuple(t_vals.shape)}")
+    require_hip(weights, "depth_loss_dense")
+    wv, tv = _f32(weights), _f32(t_vals)
+    if tv.device != wv.device:
+        raise AcnError("depth_loss_dense: t_vals must be on the weights' device")
+    N, S = wv.shape
+    z, e, ld, ls = _depth_target_args(depths, eps, depth_weight, sight_weight, N, wv.device, "depth_loss_dense")
+    rs = _ray_scale_arg(ray_scale, N, wv.device, "depth_loss_dense")
+    loss = torch.empty(N, device=wv.device, dtype=torch.float32)
+    grad = torch.empty(N, S, device=wv.device, dtype=torch.float32) if want_grad else None
+    check(_lib.lib().acn_depth_loss_dense(ptr(wv), ptr(tv), N, int(S), ptr(z), ptr(e), ptr(rs), ld, ls, ptr(loss),
+                                          ptr(grad), stream_of(wv)), "acn_depth_loss_dense")
+    return loss, grad
+
+
+SSIM_TILE_H = SSIM_TILE_W = 32  # ACN_SSIM_TILE: map pixels (forward) / image pixels (gradient) per workgroup
 SSIM_MAX_WIN = 11                # the fused path takes odd window sizes 3 .. 11
 _SSIM_WS = {}
 

@@ -1169,6 +1169,56 @@ def distortion_loss(weights: Tensor, t_vals: Tensor, rays: Optional[Tensor] = No
     return loss.mean() if reduction == "mean" else loss.sum()
 
 
+def depth_loss(weights: Tensor, t_vals: Tensor, depths: Tensor, eps, rays: Optional[Tensor] = None,
+               depth_weight: float = 1.0, sight_weight: float = 1.0, reduction: str = "mean") -> Tensor:
+    """Depth supervision of a stratified render (the expected-depth term of DS-NeRF plus the
+    line-of-sight term of Urban Radiance Fields), for the (N,S) ``weights`` and ``t_vals`` of
+    ``render_rays(..., return_t_vals=True)``.  Per ray with the target ``depths[r]`` = z (distance along the ray, the
+    unit of ``t_vals``; ``ray_sampling.point_depth_targets`` makes them from a point cloud), the half-width ``eps`` (a
+    float or (N,)) and sigma = eps / 3, over the compositing's own intervals [t_i, t_i + d_i] (d = volume_render's
+    ``dists``):
+
+        depth_weight (c (D - z))^2 + sight_weight sum_{t_i < z + eps} (w_i - k_i)^2,    D = sum_i w_i t_i
+
+    D is the ``depth`` volume_render returns; k_i is the mass the Gaussian N(z, sigma) cut at z +- eps puts into
+    interval i, so weight in front of the window pays w^2 (empty space), weight inside it is drawn to the Gaussian,
+    and weight behind it is left to occlusion.  ``rays`` (N, >=8) sets c = 1 / (far - near) (c = 1 without): the depth
+    error in units of the ray's length, 0 for a ray without far > near.  A ray whose depth or eps is not finite or
+    <= 0 (NaN marks a pixel without a target), or whose c is 0, contributes an exact 0 to loss and gradient, whatever
+    its t values.  ``reduction``: none (N,) | sum | mean, the mean over the rays that carry a target (at least 1):
+    sparse targets cover a small, varying share of a batch, and a mean over all rays would scale the term by that
+    share.  The count is taken on the device without a host read.  Differentiable in the weights (loss and gradient
+    from one HIP launch, acn_depth_loss_dense; elsewhere the same formula as float64 torch ops, differentiable any
+    number of times); the t values, targets and eps carry no gradient."""
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError(f"depth_loss: reduction must be none, mean or sum, got {reduction!r}")
+    if weights.dim() != 2 or weights.shape[1] < 2 or t_vals.shape != weights.shape:
+        raise ops.AcnError(f"depth_loss: weights and t_vals must both be (N, S >= 2), got {tuple(weights.shape)} "
+                           f"and {tuple(t_vals.shape)}")
+    ld, ls = nerfacc._check_depth_weights(depth_weight, sight_weight, "depth_loss")
+    dev = weights.device
+    z, ep = nerfacc._depth_targets(depths, eps, weights.shape[0], dev, "depth_loss")
+    scale = None
+    if rays is not None:
+        if rays.dim() != 2 or rays.shape[0] != weights.shape[0] or rays.shape[1] < 8:
+            raise ops.AcnError(f"depth_loss: rays must be ({weights.shape[0]}, >=8), got {tuple(rays.shape)}")
+        near, far = rays.detach()[:, 6].to(dev), rays.detach()[:, 7].to(dev)
+        scale = torch.where(far > near, 1.0 / (far - near), torch.zeros_like(far))
+    t = t_vals.detach().to(dev)
+    if nerfacc._distortion_fused(weights):
+        loss = nerfacc._DepthLossFn.apply(weights, t, None, None, None, None, z, ep, scale, ld, ls,
+                                          torch.is_grad_enabled() and weights.requires_grad)
+    else:
+        d = (t[:, 1:] - t[:, :-1]).clamp_min(1e-4)
+        d = torch.cat([d, d[:, -1:]], dim=1).double()
+        loss = nerfacc._depth_loss_torch(weights, t.double(), t.double() + d, t.double(), z, ep, scale, ld, ls)
+    if reduction == "none":
+        return loss
+    if reduction == "sum":
+        return loss.sum()
+    return loss.sum() / nerfacc._depth_live(z, ep, scale).sum().clamp_min(1).to(loss.dtype)
+
+
 def _normal_composite_torch(grad: Tensor, weights: Tensor) -> Tensor:
     """ops.normal_composite as torch ops (CPU models): fp32 terms, float64 sum over the samples."""
     N, S = weights.shape

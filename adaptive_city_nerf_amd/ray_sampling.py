@@ -3,6 +3,8 @@
 get_ray_directions / get_rays / clamp_rays_near_far keep the reference's signatures and output
 layouts ((H,W,3) dirs; (H,W,8) or (N,8) packed rays [o, d, near, far]); the arithmetic matches
 the reference's CPU ops (tests/test_gpu_kernels.py::test_get_rays_vs_reference).
+point_depth_targets (an extension) turns a world-space point cloud into per-pixel depth targets for
+ray_rendering.depth_loss.
 """
 from __future__ import annotations
 
@@ -106,3 +108,36 @@ def clamp_rays_near_far(rays: Tensor, near_far_override: Optional[Tuple[Optional
     """(rays', valid): optional near/far overrides; invalid rays get near=far=invalid_value
     (ray_sampling.py:139-176).  With override None the input is returned unchanged."""
     return ops.clamp_rays(rays, near_far_override, eps=eps, invalid_value=invalid_value)
+
+
+@torch.no_grad()
+def point_depth_targets(points: Tensor, c2w: Tensor, H: int, W: int, fx: float, fy: float, cx: float, cy: float,
+                        center_pixels: bool) -> Tensor:
+    """(H*W,) fp32 depth targets of one view from world points ``points`` (P, 3), e.g. the sparse SfM cloud of a
+    COLMAP reconstruction: each pixel (row-major, the order of get_ray_directions / get_rays) gets the smallest
+    distance |X - o| over the points that project into it and lie in front of the camera, NaN where there is none
+    (ray_rendering.depth_loss skips such a ray).  The camera is get_ray_directions' (RUB: x right, y up, looking
+    along -z): pixel (column i, row j) looks along ((i' - cx) / fx, -(j' - cy) / fy, -1) with i' = i + 0.5 under
+    ``center_pixels`` and i otherwise, so a point belongs to the pixel whose ray passes nearest to it: i =
+    floor(u) with centred pixels, round(u) without.  For X = o + t d on pixel p's own (unit) ray the target at p is t.
+    Plain torch ops in float64 on the points' device (once per image: no hot path)."""
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ops.AcnError(f"point_depth_targets: points must be (P, 3), got {tuple(points.shape)}")
+    H, W = int(H), int(W)
+    dev = points.device
+    X = points.detach().double()
+    c = c2w.detach().to(dev).double()[:3, :4]
+    rel = X - c[:, 3]
+    cam = rel @ c[:, :3]                                  # R^T (X - o): camera-frame coordinates
+    depth = -cam[:, 2]                                    # along the viewing direction
+    front = depth > 0
+    safe = torch.where(front, depth, torch.ones_like(depth))
+    u = float(cx) + float(fx) * cam[:, 0] / safe
+    v = float(cy) - float(fy) * cam[:, 1] / safe
+    shift = 0.0 if center_pixels else 0.5
+    i, j = torch.floor(u + shift), torch.floor(v + shift)
+    ok = front & torch.isfinite(i) & torch.isfinite(j) & (i >= 0) & (i < W) & (j >= 0) & (j < H)
+    pix = (j[ok] * W + i[ok]).long()
+    out = torch.full((H * W,), float("inf"), dtype=torch.float64, device=dev)
+    out = out.scatter_reduce(0, pix, rel[ok].norm(dim=1), reduce="amin", include_self=True)
+    return torch.where(torch.isinf(out), torch.full_like(out, float("nan")), out).float()

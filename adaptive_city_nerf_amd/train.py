@@ -28,7 +28,7 @@ from . import ops
 from ._lib import graph_capture
 from .color_space import color_space_transformer
 from .optim import FusedAdam
-from .ray_rendering import distortion_loss, interlevel_loss, render_rays
+from .ray_rendering import depth_loss, distortion_loss, interlevel_loss, render_rays
 
 
 class _MSELinearFn(torch.autograd.Function):
@@ -67,7 +67,8 @@ def compute_mse_loss(P, model, data, params=None, active_module=None, reduction:
 
 
 def compute_loss(P, model, data, params=None, active_module=None, reduction: str = "mean",
-                 distortion_weight: float = 0.0, proposal=None, interlevel_weight: float = 1.0, **render_kwargs):
+                 distortion_weight: float = 0.0, proposal=None, interlevel_weight: float = 1.0,
+                 depth_weight: float = 0.0, sight_weight: float = 0.0, depth_eps=None, **render_kwargs):
     """compute_mse_loss plus ``distortion_weight`` times the mean distortion loss of the render's weights
     (ray_rendering.distortion_loss, every ray normalised to unit length): the mip-NeRF 360 regulariser against
     semi-transparent fog and floaters between the camera and the surface.  With weight 0 it is compute_mse_loss, from
@@ -77,7 +78,16 @@ def compute_loss(P, model, data, params=None, active_module=None, reduction: str
     ``proposal`` (a density-only field, ray_rendering.proposal_weights) renders proposal-guided
     (render_rays_proposal; ``n_importance`` in the render kwargs is the number of depths the model is evaluated at,
     ``P.ray_samples`` the proposal's) and adds ``interlevel_weight`` times the mean interlevel loss, which trains the
-    proposal and carries no gradient to the model; the image loss carries none to the proposal."""
+    proposal and carries no gradient to the model; the image loss carries none to the proposal.
+
+    ``depth_weight`` / ``sight_weight`` > 0 add depth supervision (ray_rendering.depth_loss): that
+    multiple of the expected-depth term and of the line-of-sight term, against the targets ``data["depths"]`` (N,)
+    (distance along the ray; NaN where a ray has none) with the half-width ``depth_eps`` (a float or (N,)), averaged
+    over the rays that carry a target, on the weights of the pass the image loss is taken on.  With both 0 nothing
+    changes: the same calls, the same loss."""
+    geo = {}
+    if depth_weight or sight_weight:
+        geo = _depth_terms(depth_weight, sight_weight, data.get("depths"), depth_eps, "compute_loss")
     if proposal is not None:
         if not render_kwargs.get("n_importance"):
             raise ValueError("compute_loss: a proposal needs n_importance > 0 in the render arguments (the number of "
@@ -89,9 +99,11 @@ def compute_loss(P, model, data, params=None, active_module=None, reduction: str
         loss = mse_color_loss(pred_rgb, data["rgbs"], P.color_space, reduction)
         if distortion_weight:
             loss = loss + float(distortion_weight) * distortion_loss(weights, t_vals, rays=rays, reduction="mean")
+        if geo:
+            loss = loss + depth_loss(weights, t_vals, data["depths"], depth_eps, rays=rays, reduction="mean", **geo)
         return loss + float(interlevel_weight) * interlevel_loss(t_vals, weights, t_prop, w_prop, rays=rays,
                                                                  reduction="mean")
-    if not distortion_weight:
+    if not distortion_weight and not geo:
         return compute_mse_loss(P, model, data, params=params, active_module=active_module, reduction=reduction,
                                 **render_kwargs)
     gt_rgb = data["rgbs"]
@@ -99,19 +111,36 @@ def compute_loss(P, model, data, params=None, active_module=None, reduction: str
     pred_rgb, _, weights, _, t_vals = render_rays(model, rays, ray_samples=P.ray_samples, params=params,
                                                   active_module=active_module, chunk=P.chunk_points,
                                                   return_t_vals=True, **render_kwargs)
-    return mse_color_loss(pred_rgb, gt_rgb, P.color_space, reduction) + \
-        float(distortion_weight) * distortion_loss(weights, t_vals, rays=rays, reduction="mean")
+    loss = mse_color_loss(pred_rgb, gt_rgb, P.color_space, reduction)
+    if distortion_weight:
+        loss = loss + float(distortion_weight) * distortion_loss(weights, t_vals, rays=rays, reduction="mean")
+    if geo:
+        loss = loss + depth_loss(weights, t_vals, data["depths"], depth_eps, rays=rays, reduction="mean", **geo)
+    return loss
+
+
+def _depth_terms(depth_weight, sight_weight, depths, depth_eps, what: str) -> dict:
+    """{} with both weights 0 (no depth supervision), else depth_loss's two weights, after checking that the targets
+    and the half-width are there."""
+    if not depth_weight and not sight_weight:
+        return {}
+    if depths is None or depth_eps is None:
+        raise ValueError(f"{what}: depth_weight / sight_weight need the target depths and depth_eps")
+    return {"depth_weight": float(depth_weight), "sight_weight": float(sight_weight)}
 
 
 def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Optional[float] = 1.0,
                group=None, shared: Optional[list] = None, grad_scaler=None, distortion_weight: float = 0.0,
-               proposal=None, interlevel_weight: float = 1.0, **render_kwargs) -> torch.Tensor:
+               proposal=None, interlevel_weight: float = 1.0, depths=None, depth_weight: float = 0.0,
+               sight_weight: float = 0.0, depth_eps=None, **render_kwargs) -> torch.Tensor:
     """One optimizer update of runtime_adapt (runtime_adapt.py:288-313).  Returns the loss (device).
     ``distortion_weight`` > 0 adds that multiple of the mean distortion loss (compute_loss) to the MSE.
     ``n_importance`` = K > 0 (through ``render_kwargs``, with ``jitter_fine``) trains on the coarse-to-fine render
     (render_rays_hierarchical): the loss is taken on the fine pass.
     ``proposal`` (with ``n_importance``) trains on the proposal-guided render and adds ``interlevel_weight`` times the
     interlevel loss (compute_loss), which trains the proposal: its parameters must be in ``optimizer``.
+    ``depth_weight`` / ``sight_weight`` > 0 add depth supervision against ``depths`` (N,) with the half-width
+    ``depth_eps`` (compute_loss); with both 0, ``depths`` is not looked at.
 
     ``group`` (expert parallel): ``rays`` / ``rgbs`` are this rank's shard of the global batch, the
     container's experts are distributed over the group (expert_parallel.adapt_step_expert_parallel);
@@ -122,6 +151,10 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
     if group is not None and distortion_weight:
         raise ValueError("adapt_step: the expert-parallel step has no distortion loss (distortion_weight must be 0 "
                          "with a group)")
+    if group is not None and (depth_weight or sight_weight):
+        raise ValueError("adapt_step: the expert-parallel step has no depth supervision (depth_weight and sight_weight "
+                         "must be 0 with a group)")
+    geo = _depth_terms(depth_weight, sight_weight, depths, depth_eps, "adapt_step")
     if group is not None and render_kwargs.get("n_importance"):
         raise ValueError("adapt_step: the expert-parallel step renders one stratified pass (n_importance must be 0 "
                          "with a group)")
@@ -143,7 +176,11 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
                                           shared, grad_clip=grad_clip, group=group,
                                           u=render_kwargs.get("jitter_u"))
     optimizer.zero_grad()
-    loss = compute_loss(P, model=base, data={"rays": rays, "rgbs": rgbs}, params=None, active_module=active_module,
+    data = {"rays": rays, "rgbs": rgbs}
+    if geo:
+        data["depths"] = depths
+        render_kwargs = dict(render_kwargs, depth_eps=depth_eps, **geo)
+    loss = compute_loss(P, model=base, data=data, params=None, active_module=active_module,
                         reduction="mean", distortion_weight=distortion_weight, proposal=proposal,
                         interlevel_weight=interlevel_weight, **render_kwargs)
     # without FusedAdam the clip norm is taken over the base's and the proposal's parameters together
@@ -180,11 +217,13 @@ class GraphedAdaptStep:
     per-expert index selection is data-dependent.  Expert-parallel groups are not captured (use
     adapt_step).  ``distortion_weight`` as in adapt_step: the distortion launch and its backward multiply make no
     host synchronisation, so they are captured with the rest.  The proposal-guided step is not captured (use
-    adapt_step)."""
+    adapt_step).  ``depth_weight`` / ``sight_weight`` as in adapt_step: ``depths`` (N,) is copied into a static buffer
+    before each replay (pass ``depths=`` per call), ``depth_eps`` is fixed at capture; the depth launch and the count
+    of rays with a target make no host synchronisation."""
 
     def __init__(self, P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Optional[float] = 1.0,
                  warmup: int = 2, max_steps: int = 1 << 16, distortion_weight: float = 0.0, proposal=None,
-                 **render_kwargs):
+                 depths=None, depth_weight: float = 0.0, sight_weight: float = 0.0, depth_eps=None, **render_kwargs):
         from .meta_container import MetaContainer
         if proposal is not None:
             raise ValueError("GraphedAdaptStep: the proposal-guided render is not captured; use adapt_step")
@@ -203,6 +242,13 @@ class GraphedAdaptStep:
             render_kwargs = dict(render_kwargs, jitter_u=self.static_u)
         if distortion_weight:
             render_kwargs = dict(render_kwargs, distortion_weight=float(distortion_weight))
+        self.static_depths = None
+        geo = _depth_terms(depth_weight, sight_weight, depths, depth_eps, "GraphedAdaptStep")
+        if geo:
+            self.static_depths = depths.detach().to(rays.device, torch.float32).reshape(-1).clone()
+            if isinstance(depth_eps, torch.Tensor):
+                depth_eps = depth_eps.detach().to(rays.device, torch.float32).clone()
+            render_kwargs = dict(render_kwargs, depths=self.static_depths, depth_eps=depth_eps, **geo)
         self.args = (P, base, optimizer, active_module, grad_clip, render_kwargs)
         side = torch.cuda.Stream(rays.device)
         side.wait_stream(torch.cuda.current_stream(rays.device))
@@ -222,7 +268,8 @@ class GraphedAdaptStep:
         self.replays = 0
         self.max_steps = int(max_steps)
 
-    def __call__(self, rays: torch.Tensor, rgbs: torch.Tensor, jitter_u: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def __call__(self, rays: torch.Tensor, rgbs: torch.Tensor, jitter_u: Optional[torch.Tensor] = None,
+                 depths: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self.replays >= self.max_steps:
             # past the precomputed Adam table the captured update would silently stop
             raise RuntimeError(f"GraphedAdaptStep: {self.max_steps} replays exhausted the Adam constant table; "
@@ -231,6 +278,10 @@ class GraphedAdaptStep:
         self.static_rgbs.copy_(rgbs, non_blocking=True)
         if jitter_u is not None:
             self.static_u.copy_(jitter_u, non_blocking=True)
+        if depths is not None:
+            if self.static_depths is None:
+                raise ValueError("GraphedAdaptStep: captured without depth supervision; depths cannot be replayed")
+            self.static_depths.copy_(depths.reshape(-1), non_blocking=True)
         self.graph.replay()
         self.replays += 1
         from .optim import bump_versions
@@ -277,7 +328,8 @@ FAST_RUNTIME_ADAPT = os.environ.get("ACN_FAST_ADAPT", "1") != "0"
 def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional[int] = None,
                   active_module: Optional[int] = None, grad_clip: Optional[float] = 1.0,
                   distortion_weight: float = 0.0, proposal=None, interlevel_weight: float = 1.0,
-                  n_importance: int = 0) -> Dict[str, float]:
+                  n_importance: int = 0, depth_weight: float = 0.0, sight_weight: float = 0.0,
+                  depth_eps=None) -> Dict[str, float]:
     """runtime_adapt.py:213-315: adapt in place; one pass over the loader (steps=None) or exactly
     ``steps`` updates cycling over it.
 
@@ -290,7 +342,12 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
     kernel has no regulariser, so none is built), and every configuration with ``n_importance`` > 0 or a
     ``proposal``: the proposal-guided step evaluates the model at ``n_importance`` depths and adds
     ``interlevel_weight`` times the interlevel loss; the proposal, whose parameters must be in ``optimizer``, is put in
-    training mode too."""
+    training mode too.  ``depth_weight`` / ``sight_weight`` > 0 add depth supervision (adapt_step) and take the eager
+    step as well: the loader then yields (rays, rgbs, depths), ``depth_eps`` is the half-width.  With both 0 the loader
+    may yield pairs or triples; the depths are not used."""
+    geo = bool(depth_weight or sight_weight)
+    if geo and depth_eps is None:
+        raise ValueError("runtime_adapt: depth_weight / sight_weight need depth_eps")
     device = next(model.parameters()).device
     model.train()
     if proposal is not None:
@@ -304,15 +361,22 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
         extra.update(proposal=proposal, interlevel_weight=interlevel_weight)
     if n_importance:
         extra["n_importance"] = int(n_importance)
+    if geo:
+        extra.update(depth_weight=float(depth_weight), sight_weight=float(sight_weight), depth_eps=depth_eps)
     fast = [None, active_module is None and not distortion_weight and not extra]   # [RoutedAdaptStep, worth trying]
     # use_amp: a fresh GradScaler per call (runtime_adapt.py:237); the cached RoutedAdaptStep's scaler restarts too
     amp = ops.TRAIN_MLP_PRECISION == "amp"
     scaler = torch.amp.GradScaler("cuda") if amp else None
     reset = set()
 
-    def run(rays, rgbs):
+    def run(rays, rgbs, depths=None):
         nonlocal last_loss, step_count
         rays, rgbs = rays.to(device, non_blocking=True), rgbs.to(device, non_blocking=True)
+        more = {}
+        if geo:
+            if depths is None:
+                raise ValueError("runtime_adapt: depth_weight / sight_weight need loader items (rays, rgbs, depths)")
+            more["depths"] = depths.to(device, non_blocking=True)
         if fast[1] and (fast[0] is None or rays.shape[0] > fast[0].N):
             fast[0] = _routed_step_for(P, base, optimizer, int(rays.shape[0]), grad_clip)
             fast[1] = fast[0] is not None
@@ -323,21 +387,21 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
             last_loss = fast[0](rays, rgbs)
         else:
             last_loss = adapt_step(P, base, rays, rgbs, optimizer, active_module=active_module, grad_clip=grad_clip,
-                                   grad_scaler=scaler, distortion_weight=distortion_weight, **extra)
+                                   grad_scaler=scaler, distortion_weight=distortion_weight, **extra, **more)
         step_count += 1
 
     if steps is None:
-        for rays, rgbs in data_loader:
-            run(rays, rgbs)
+        for item in data_loader:
+            run(*item)
     else:
         it = iter(data_loader)
         while step_count < int(steps):
             try:
-                rays, rgbs = next(it)
+                item = next(it)
             except StopIteration:
                 it = iter(data_loader)
-                rays, rgbs = next(it)
-            run(rays, rgbs)
+                item = next(it)
+            run(*item)
     if fast[0] is not None:
         fast[0].sync_state()   # host state['step'] current (state_dict, a later eager step)
     return {"loss": 0.0 if last_loss is None else float(last_loss), "steps": step_count}

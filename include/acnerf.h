@@ -615,6 +615,36 @@ int acn_distortion_packed(const float* weights, const float* t_starts, const flo
                           float* loss, float* grad_w, void* stream);
 int acn_distortion_dense(const float* weights, const float* t_vals, int64_t N, int S, const float* ray_scale,
                          float* loss, float* grad_w, void* stream);
+/* Depth supervision of the weights along each ray and its gradient in the weights, in one launch (the expected-depth
+ * term of DS-NeRF plus the line-of-sight term of Urban Radiance Fields; the t values, the targets and the half-widths
+ * carry no gradient).  For ray r with target depth z = depth[r], half-width e = eps[r], scale c = ray_scale[r]:
+ *   sigma = e / 3, lo = z - e, hi = z + e, Phi the standard normal CDF
+ *   k_i      = Phi((min(e_i, hi) - z) / sigma) - Phi((max(s_i, lo) - z) / sigma) if min(e_i, hi) > max(s_i, lo), else 0
+ *   m_i      = 1 if s_i < hi else 0
+ *   D        = sum_i w_i tau_i
+ *   loss[r]  = depth_weight (c (D - z))^2 + sight_weight sum_i m_i (w_i - k_i)^2
+ *   grad_w_i = 2 depth_weight c^2 (D - z) tau_i + 2 sight_weight m_i (w_i - k_i)
+ * over the ray's intervals [s_i, e_i] with per-sample depths tau_i: k_i is the mass a Gaussian of deviation e / 3 cut
+ * at +-e around the target puts into interval i; a sample in front of the window pays w^2, one overlapping it
+ * (w - k)^2, one wholly behind it (s_i >= hi) nothing.  One wave per ray, 64 samples per step; all arithmetic from the
+ * fp32 inputs on in float64 (Phi through erf), loss and gradient rounded to fp32 once.  No atomics: bitwise
+ * reproducible.
+ * packed: samples (M,) with s = t_starts, e = t_ends, tau = (s + e) / 2; ray r owns samples chunk_starts[r] .. +
+ *   chunk_cnts[r] (a range is cut at M; an empty ray has D = 0 and no gradient).
+ * dense: w and t_vals (N, S), S >= 2, with the compositing's own intervals: s_i = tau_i = t_i (D is
+ *   acn_volume_render_fwd's depth), e_i = t_i + d_i, d_i = max(t_{i+1} - t_i, 1e-4) in fp32 and the last d copied from
+ *   its predecessor (acn_volume_render_fwd's dists).
+ * depth, eps (N): a ray whose depth or eps is not finite or <= 0 has no target.  ray_scale (N) or NULL (c = 1).  A ray
+ *   without a target or with c exactly 0.0f is skipped: zeros are written and its t values are not read (an invalid ray
+ *   with NaN bounds poisons nothing).  depth_weight, sight_weight >= 0.
+ * grad_w (M) / (N, S) or NULL (loss only; the same loss bits).  N == 0 is a no-op. */
+int acn_depth_loss_packed(const float* weights, const float* t_starts, const float* t_ends, int64_t M,
+                          const int64_t* chunk_starts, const int64_t* chunk_cnts, int64_t N, const float* depth,
+                          const float* eps, const float* ray_scale, double depth_weight, double sight_weight,
+                          float* loss, float* grad_w, void* stream);
+int acn_depth_loss_dense(const float* weights, const float* t_vals, int64_t N, int S, const float* depth,
+                         const float* eps, const float* ray_scale, double depth_weight, double sight_weight,
+                         float* loss, float* grad_w, void* stream);
 /* Hierarchical importance resampling (classic NeRF sample_pdf) of the weights of a coarse pass, in one launch: F new
  * depths per ray by the inverse CDF of the piecewise-constant density the inner weights describe, the row merged with
  * the coarse depths and, optionally, the sample points.  Per ray, in float64 on the fp32 inputs (t_vals non-decreasing,
