@@ -25,6 +25,7 @@ a CPU restatement in to check the data movement over gloo.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -33,8 +34,16 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
-from ._lib import graph_capture
+# routed_train through the module: its hooks and switches (EVENT_HOOK, JITTER, ...) are read at call time
+from . import _lib, ops, routed_train as RT
+from ._lib import AcnError, check, graph_capture, ptr
 from .color_space import color_space_transformer
+from .meta_container import MetaContainer
+from .meta_ngp import _FusedMLPFn
+from .optim import FusedAdam, bump_versions
+from .parallel import contiguous_plan, gather_rendered, local_sse, psnr_reduce
+from .ray_rendering import ENC_EPS, _BlendFn, _fused_background, _get_bg_rgb, volume_render
+from .train import mse_color_loss
 
 
 # ExpertParallelRenderer's record order: depth tiles of this many neighbouring rays (0: sample order; env
@@ -141,8 +150,6 @@ def adapt_step_expert_parallel(P, backend, rays: Tensor, rgbs: Tensor, optimizer
     experts get the complete gradients of the samples routed to them from every rank; the ``shared``
     background head is all-reduced; the clip norm is global (shared parameters counted once).  Returns the
     global MSE (device)."""
-    from . import ops
-    from .optim import FusedAdam
     if ops.TRAIN_MLP_PRECISION == "amp":
         raise ValueError("adapt_step_expert_parallel: the use_amp MLP precision needs a loss scale; select 'fp16x3' "
                          "or 'fp32' for expert-parallel steps")
@@ -207,7 +214,6 @@ class HipBackend:
         self.bg_color_default = bg_color_default
 
     def pairs(self, rays: Tensor, S: int, u: Optional[Tensor]) -> PairSet:
-        from . import ops
         m = self.model
         if m.training and u is None:
             u = torch.rand_like(rays.new_empty(rays.shape[0], S))  # the reference's rand_like(low) draw
@@ -216,9 +222,6 @@ class HipBackend:
         return PairSet(t, counts, pidx, pw, xd, pmap, pk)
 
     def expert(self, k: int, xd: Tensor) -> Tensor:
-        from . import ops
-        from .meta_ngp import _FusedMLPFn
-        from .ray_rendering import ENC_EPS
         sub = self.model.submodules[k]
         if not sub.uses_grad():
             return sub(xd)   # the fused MFMA field kernel (eval)
@@ -229,11 +232,9 @@ class HipBackend:
         return _FusedMLPFn.apply(h0.contiguous(), sh, *ws)
 
     def blend(self, y: Tensor, ps: PairSet) -> Tensor:
-        from .ray_rendering import _BlendFn
         return _BlendFn.apply(y.contiguous(), ps.pw, ps.pmap, ps.pidx)
 
     def composite(self, rs: Tensor, t: Tensor, rays: Tensor):
-        from .ray_rendering import _get_bg_rgb, volume_render
         bg = _get_bg_rgb(self.model, rays[:, 3:6], None, rs, N=rays.shape[0], bg_color_default=self.bg_color_default)
         return volume_render(rs, t, bg_rgb=bg, raw_rgb=False, raw_sigma=False)
 
@@ -267,10 +268,6 @@ class ExpertParallelRenderer:
     def __init__(self, model, n_rays: int, ray_samples: int, group=None, capacity: Optional[int] = None,
                  graph: bool = False, bg_color_default: str = "white", want_weights: bool = False,
                  tile_rays: Optional[int] = None):
-        from . import _lib, ops
-        from ._lib import AcnError
-        from .meta_container import MetaContainer
-        from .ray_rendering import _fused_background
         if not isinstance(model, MetaContainer) or not all(s._fusable for s in model.submodules):
             raise AcnError("ExpertParallelRenderer: a MetaContainer of reference-configuration experts is required")
         self.comm = comm = _Comm(group)
@@ -343,9 +340,6 @@ class ExpertParallelRenderer:
         self.last_exchange = None    # bytes this rank sent in the last call: {"sent": .., "live": ..}
 
     def _run(self, n: int) -> None:
-        import ctypes as C
-        from . import _lib, ops
-        from ._lib import check, ptr
         L = _lib.lib()
         s = int(torch.cuda.current_stream(self.device).cuda_stream)
         K, E, S, Cc, comm = self.K, self.E, self.S, self.C, self.comm
@@ -379,9 +373,6 @@ class ExpertParallelRenderer:
         """One batch with the exchange sized by ``counts`` (host (W, K) ints: every rank's pair counts of this
         batch, the capacities of its segments): compact layouts on both sides, no padding slot crosses a link.
         ``recv_cnt``: the (W, E) counts of the owned experts on the device (int64; read by the field kernel)."""
-        import ctypes as C
-        from . import _lib
-        from ._lib import check, ptr
         L = _lib.lib()
         s = int(torch.cuda.current_stream(self.device).cuda_stream)
         K, E, W, S, comm, rank, own, owner = self.K, self.E, self.W, self.S, self.comm, self.comm.rank, self.own, self.owner
@@ -402,7 +393,6 @@ class ExpertParallelRenderer:
             check(L.acn_pack_experts(self._own_arr, C.byref(self.own_routing), -1, ptr(self.packed),
                                      self.packed.numel() * 4, s), "acn_pack_experts")
         if pr > 0:
-            from . import ops
             hook = ops.EVENT_HOOK   # bench.py timing (eager only: this path is never captured)
             if hook is not None:
                 e0 = torch.cuda.Event(enable_timing=True)
@@ -427,7 +417,6 @@ class ExpertParallelRenderer:
         """As __call__, with the exchange sized by ``counts`` (host (W, K): every rank's pair counts of this batch,
         acn_routed_count_batches).  Eager (the split sizes change per batch); collective over the group.
         ``recv_cnt``: counts[w][own[e]] as a device int64 (W * E) tensor, if the caller already holds one."""
-        from ._lib import AcnError
         n = int(rays.shape[0])
         if rays.dim() != 2 or rays.shape[1] != 8 or not 0 < n <= self.N:
             raise AcnError(f"ExpertParallelRenderer was built for up to {self.N} rays per rank; got {tuple(rays.shape)}")
@@ -442,7 +431,6 @@ class ExpertParallelRenderer:
     def __call__(self, rays: Tensor):
         """(rgb (n,3), depth (n,), weights (n,S) or None, acc (n,)) of this rank's ``rays`` (n <= n_rays): views
         of persistent buffers, valid until the next call.  Collective over the group."""
-        from ._lib import AcnError
         n = int(rays.shape[0])
         if rays.dim() != 2 or rays.shape[1] != 8 or not 0 < n <= self.N:
             raise AcnError(f"ExpertParallelRenderer was built for up to {self.N} rays per rank; got {tuple(rays.shape)}")
@@ -547,9 +535,6 @@ def render_rays_ep_batched(model, rays: Tensor, ray_samples: int, group=None, ba
 
 def _render_planned(model, rays: Tensor, S: int, group, batch: int, nb: int, stats: Optional[dict]):
     """render_rays_ep_batched's planned exchange (see there)."""
-    import ctypes as C
-    from . import _lib
-    from ._lib import AcnError, check, ptr
     world, rank = world_rank(group)
     n = int(rays.shape[0])
     dev = rays.device
@@ -610,10 +595,8 @@ def render_image_expert_parallel(model, *, H: int, W: int, fx: float, fy: float,
     band of the frame's pixels through render_rays_expert_parallel (its samples' records go to the
     experts' owners), then the rendered rows are all-gathered and the PSNR all-reduced (parallel.py).
     Returns (rgb (H,W,3) clamped, depth (H*W,), acc (H*W,), psnr or None)."""
-    from .parallel import contiguous_plan, gather_rendered, local_sse, psnr_reduce
     world, rank = world_rank(group)
     if rays is None:
-        from . import ops
         device = next(model.parameters()).device
         rays, _ = ops.get_rays_image(H, W, fx, fy, cx, cy, c2w, scene_box.aabb, device, center_pixels=center_pixels,
                                      near_far_override=(None, None), apply_clamp=True)
@@ -750,24 +733,7 @@ class ExpertParallelAdaptStep:
                  grad_clip: Optional[float] = 1.0, group=None, graph: bool = False, warmup: int = 1,
                  jitter: str = "draw", clear_in_adam: bool = True, max_steps: int = 1 << 16,
                  capacity: Optional[int] = None):
-        import ctypes as C
-        import numpy as np
-        from . import _lib, ops
-        from ._lib import AcnError, acn_mlp
-        from .meta_container import MetaContainer
-        from .optim import NORM_ELSEWHERE_FLAG, ZERO_GRAD_FLAG, FusedAdam, SlottedAdam
-        from .routed_train import ALIGN, FUSED_BACKGROUND, TELESCOPED_TABLE_NORM
-        if not isinstance(model, MetaContainer) or not all(s._fusable for s in model.submodules):
-            raise AcnError("ExpertParallelAdaptStep: a MetaContainer of reference-configuration experts is required")
-        if not isinstance(optimizer, FusedAdam):
-            raise AcnError("ExpertParallelAdaptStep needs FusedAdam")
-        if not model.use_bg_nerf:
-            raise AcnError("ExpertParallelAdaptStep: the background head is part of the reference configuration")
-        encs = [s.xyz_encoder for s in model.submodules]
-        e0 = encs[0]
-        if any(e._res_host != e0._res_host or e.log2_hashmap_size != e0.log2_hashmap_size
-               or e._interp_code != e0._interp_code for e in encs) or e0._interp_code == 0:
-            raise AcnError("ExpertParallelAdaptStep: experts must share one Linear/Smoothstep hash-grid configuration")
+        RT.check_routed_config("ExpertParallelAdaptStep", model, optimizer)
         self.comm = comm = _Comm(group)
         W, rank = comm.world, comm.rank
         self.P, self.model, self.opt, self.grad_clip = P, model, optimizer, grad_clip
@@ -779,15 +745,18 @@ class ExpertParallelAdaptStep:
                            "carry; select 'fp16x3' or 'fp32' (ops.set_train_mlp_precision)")
         self.jitter_mode = jitter
         self.clear_in_adam = bool(clear_in_adam)
-        self.tele = TELESCOPED_TABLE_NORM and grad_clip is not None
-        dev = e0.hash_table.device
-        self.device = dev
         K = len(model.submodules)
         owner = expert_owner(K, W)
         own = [k for k in range(K) if owner[k] == rank]
         if not own:
             raise AcnError(f"ExpertParallelAdaptStep: rank {rank} owns no expert (K = {K} < W = {W})")
         E = len(own)
+        # the owned experts' gradients, kernel arguments and shared launches; the (replicated) head's gradients in
+        # one flat buffer for their all-reduce
+        self.bank = bank = RT.ExpertBank(model, optimizer, own, self.mlp_precision, grad_clip, self.clear_in_adam,
+                                         flat_head=True)
+        self.tele, self.gtables, self.dw = bank.tele, bank.gtables, bank.dw
+        dev = self.device = bank.device
         eo = [owner.count(o) for o in range(W)]      # experts per owner (contiguous blocks)
         S, N = int(P.ray_samples), int(n_rays)
         M = N * S
@@ -829,7 +798,7 @@ class ExpertParallelAdaptStep:
         self.rgbs_dirs = torch.zeros(N, 3, **f32)
         # ---- owner buffers
         R = W * E * Cc                                   # received records
-        cap = R + E * ALIGN                              # compact slots (segments padded to ALIGN)
+        cap = R + E * RT.ALIGN                           # compact slots (segments padded to ALIGN)
         self.recv_cnt = torch.zeros(W * E, **i64)
         self.recv_xd = torch.empty(R, 6, **f32)
         self.eseg = torch.zeros(2 * E + 1, **i64)
@@ -847,61 +816,13 @@ class ExpertParallelAdaptStep:
         self.recv_gy = torch.empty(R, 4, **f32)
         self.mws = torch.empty(int(ops.mlp_fn("acn_mlp_pairs_workspace_bytes", self.mlp_precision)(E)), device=dev,
                                dtype=torch.uint8)
-        self.dw = torch.zeros(E, ops.MLP_DW_FLOATS, **f32)
         self.loss = torch.zeros((), **f32)
         self.loss_global = torch.zeros(1, **f32)
         self.ovf = torch.zeros(1, **i64)                # global overflow flag of the last step (device)
         self.ovf_host = torch.zeros(1, dtype=torch.int64, pin_memory=True)
         self.keep = torch.ones((), **f32)               # 1 - overflow: gates the upstream gradients
         self.ovf_b = torch.zeros(1, device=dev, dtype=torch.bool)
-        # ---- persistent gradients of the owned experts and the (replicated) background head
-        self.gtables = [torch.zeros_like(encs[k].hash_table) for k in own]
-        self.bg_params = list(model.bg_mlp.parameters())
-        nbg = sum(p.numel() for p in self.bg_params)
-        self.gbg_flat = torch.zeros(nbg, **f32)
-        self.gbg, o = [], 0
-        for p in self.bg_params:
-            self.gbg.append(self.gbg_flat[o:o + p.numel()].view_as(p))
-            o += p.numel()
-        try:
-            self.bg_spec, self._bg_keep = model.background_spec() if FUSED_BACKGROUND else (None, None)
-        except AcnError:
-            self.bg_spec, self._bg_keep = None, None
-        slot_of, zero_of = {}, set()
-        for j, k in enumerate(own):
-            sub = model.submodules[k]
-            sub.xyz_encoder.hash_table.grad = self.gtables[j]
-            slot_of[id(sub.xyz_encoder.hash_table)] = j
-            zero_of.add(id(sub.xyz_encoder.hash_table))
-            views, off = [], 0
-            for shp in ops.MLP_DW_SHAPES:
-                n = int(np.prod(shp))
-                views.append(self.dw[j, off:off + n].view(shp))
-                off += n
-            for (name, t), g in zip(sub._mlp_tensors(None).items(), views):
-                t.grad = g
-                slot_of[id(t)] = j
-        for p, g in zip(self.bg_params, self.gbg):
-            p.grad = g
-            slot_of[id(p)] = E
-        self._mlp_structs = [ops._mlp_struct([t for t in model.submodules[k]._mlp_tensors(None).values()]) for k in own]
-        self._mlp_ptrs = (C.POINTER(acn_mlp) * E)(*[C.pointer(w) for w in self._mlp_structs])
-        self._tables = (C.c_void_p * E)(*[encs[k].hash_table.data_ptr() for k in own])
-        self._gtables = (C.c_void_p * E)(*[g.data_ptr() for g in self.gtables])
-        self._res = (C.c_int32 * len(e0._res_host))(*e0._res_host)
-        boxes = [model.submodules[k]._host_box() for k in own]
-        self._mins = (C.c_float * (3 * E))(*[float(v) for b in boxes for v in b[0]])
-        self._exts = (C.c_float * (3 * E))(*[float(v) for b in boxes for v in b[1]])
-        lo = np.float32(1e-6)
-        self._lo, self._hi = C.c_float(lo), C.c_float(np.float32(1.0) - lo)
-        self.routing = model.routing_spec()
-        grads = {i: None for i in slot_of}
-        for p in model.parameters():
-            if id(p) in slot_of:
-                grads[id(p)] = p.grad
-        flags = {i: (ZERO_GRAD_FLAG if self.clear_in_adam else 0) | (NORM_ELSEWHERE_FLAG if self.tele else 0)
-                 for i in zero_of}
-        self.adam = SlottedAdam(optimizer, slot_of, grads, E, E + 1, flags, max_steps=max_steps, split_norm=W > 1)
+        self.adam = bank.slotted_adam(max_steps=max_steps, split_norm=W > 1)
         self.table_sumsq = torch.zeros(1, device=dev, dtype=torch.float64)
         self._params = [r[0] for r in self.adam.rows]
         self.replays = 0
@@ -912,7 +833,6 @@ class ExpertParallelAdaptStep:
 
     def _set_caps(self, caps) -> None:
         """Per-expert segment capacities (identical on every rank) and the layouts / split sizes they imply."""
-        import ctypes as C
         self.caps = [int(max(1, min(self.M, c))) for c in caps]
         self.caps_dev.copy_(torch.tensor(self.caps, dtype=torch.int64))
         self._caps_c = (C.c_int64 * self.K)(*self.caps)
@@ -930,12 +850,6 @@ class ExpertParallelAdaptStep:
         return 8 * self.K + 24 * self.slots_send + 16 * self.slots_recv + 16 * self.slots_send
 
     def _step(self, n: int, full: bool = False) -> None:
-        import ctypes as C
-        from . import _lib, ops
-        from ._lib import check, ptr
-        from .ray_rendering import volume_render
-        from .routed_train import ALIGN, JITTER
-        from .train import mse_color_loss
         L = _lib.lib()
         saved = None
         if full and self.bounded:      # the full-capacity re-run of an overflowed step
@@ -943,17 +857,17 @@ class ExpertParallelAdaptStep:
             self._set_caps([self.M] * self.K)
         bounded = self.bounded
         Cc = self.C
-        dev, K, E, S, comm = self.device, self.K, self.E, self.S, self.comm
+        dev, K, E, S, comm, b = self.device, self.K, self.E, self.S, self.comm, self.bank
         s = int(torch.cuda.current_stream(dev).cuda_stream)
         M = n * S
         if not self.clear_in_adam:
-            for g in self.gtables:
+            for g in b.gtables:
                 g.zero_()
         u, t = self.u[:n], self.t[:n]
         if self.jitter_mode == "draw":
-            u.copy_(JITTER(n, S, dev))   # the reference's rand_like(low) draw
+            u.copy_(RT.JITTER(n, S, dev))   # the reference's rand_like(low) draw
         # sender: pairs in the fixed owner-grouped layout
-        check(L.acn_routed_count_caps(ptr(self.rays), n, S, ptr(u), C.byref(self.routing), self._caps_c, ptr(t),
+        check(L.acn_routed_count_caps(ptr(self.rays), n, S, ptr(u), C.byref(b.routing), self._caps_c, ptr(t),
                                       ptr(self.seg), ptr(self.rws), self.rws.numel(), s), "acn_routed_count_caps")
         check(L.acn_routed_scatter_xd(ptr(self.rays), n, S, K, ptr(t), ptr(self.seg), ptr(self.rws), ptr(self.pidx),
                                       ptr(self.pw), ptr(self.xd), ptr(self.pmap), ptr(self.pk), s),
@@ -968,18 +882,11 @@ class ExpertParallelAdaptStep:
         comm.all_to_all(self.recv_cnt, self.seg[K + 1:], self.split_cnt_recv, self.split_cnt_send)
         comm.all_to_all(self.recv_xd[:self.slots_recv], self.xd[:self.slots_send], self.split_recv, self.split_send)
         # owner: compact pair lists of the owned experts, field, results back into the received layout
-        check(L.acn_ep_gather_caps(ptr(self.recv_xd), ptr(self.recv_cnt), self.W, E, self._own_caps_c, ALIGN,
-                              C.cast(self._mins, C.c_void_p), C.cast(self._exts, C.c_void_p), self._lo, self._hi,
+        check(L.acn_ep_gather_caps(ptr(self.recv_xd), ptr(self.recv_cnt), self.W, E, self._own_caps_c, RT.ALIGN,
+                              C.cast(b._mins, C.c_void_p), C.cast(b._exts, C.c_void_p), b._lo, b._hi,
                               ptr(self.eseg), ptr(self.ews), ptr(self.x01), ptr(self.sh), ptr(self.pkl),
                               ptr(self.pflag), ptr(self.back), s), "acn_ep_gather")
-        enc = self.model.submodules[self.own[0]].xyz_encoder
-        check(L.acn_hashgrid_fwd_pairs(ptr(self.x01), ptr(self.pkl), ptr(self.eseg), E, self._tables, self._res,
-                                       len(enc._res_host), enc.log2_hashmap_size, enc._interp_code, ptr(self.h0), s),
-              "acn_hashgrid_fwd_pairs")
-        mfn = lambda name: ops.mlp_fn(name, self.mlp_precision)  # noqa: E731
-        check(mfn("acn_mlp_pack_pairs")(self._mlp_ptrs, E, ptr(self.mws), s), "acn_mlp_pack_pairs")
-        check(mfn("acn_mlp_train_fwd_pairs")(ptr(self.h0), ptr(self.sh), ptr(self.eseg), E, ptr(self.mws), ptr(self.out), s),
-              "acn_mlp_train_fwd_pairs")
+        b.forward(self.x01, self.pkl, self.eseg, self.sh, self.h0, self.out, self.mws)
         check(L.acn_ep_scatter_back(ptr(self.out), ptr(self.back), ptr(self.eseg), E, ptr(self.ret), s),
               "acn_ep_scatter_back")
         comm.all_to_all(self.yr[:self.slots_send], self.ret[:self.slots_recv], self.split_send, self.split_recv)
@@ -989,40 +896,37 @@ class ExpertParallelAdaptStep:
         # the loss averages over the global batch: a full batch is n_global / W rays per rank (weak) or the
         # configured share (strong); a ragged batch (n < n_rays, world size 1 only) averages over its own n rays
         frac = float(n) / float(self.n_global) if n == self.N else 1.0
-        if self.bg_spec is not None:
+        if b.bg_spec is not None:
             dirs.copy_(rays[:, 3:6])
-            bg = ops.background_fwd(dirs, self.bg_spec).requires_grad_(True)
+            bg = ops.background_fwd(dirs, b.bg_spec).requires_grad_(True)
             with torch.enable_grad():
                 rgb = volume_render(rs, t, bg_rgb=bg)[0]
                 loss = mse_color_loss(rgb, rgbs, self.P.color_space) * frac
                 g_rs, g_bg = torch.autograd.grad(loss, [rs, bg])
             if bounded:
                 g_rs, g_bg = g_rs * self.keep, g_bg * self.keep
-            ops.background_bwd(dirs, self.bg_spec, g_bg, self.gbg)
+            ops.background_bwd(dirs, b.bg_spec, g_bg, b.gbg)
         else:
             with torch.enable_grad():
                 bg = self.model.background_color(rays[:, 3:6])
                 rgb = volume_render(rs, t, bg_rgb=bg)[0]
                 loss = mse_color_loss(rgb, rgbs, self.P.color_space) * frac
-                grads = torch.autograd.grad(loss, [rs] + self.bg_params)
+                grads = torch.autograd.grad(loss, [rs] + b.bg_params)
             g_rs = grads[0] * self.keep if bounded else grads[0]
-            for g, buf in zip(grads[1:], self.gbg):
+            for g, buf in zip(grads[1:], b.gbg):
                 buf.copy_(g * self.keep if bounded else g)
         self.loss.copy_(loss.detach())
-        comm.all_reduce(self.gbg_flat)
+        comm.all_reduce(b.gbg_flat)
         gy = ops.routed_blend_bwd(g_rs.reshape(M, 4).contiguous(), self.pidx[:self.slots_send], self.pw[:self.slots_send])
         comm.all_to_all(self.recv_gy[:self.slots_recv], gy, self.split_recv, self.split_send)
         # owner: backward of the owned experts
         check(L.acn_ep_gather_grad(ptr(self.recv_gy), ptr(self.back), ptr(self.eseg), E, ptr(self.gout), s),
               "acn_ep_gather_grad")
-        check(mfn("acn_mlp_train_bwd_dw_pairs")(ptr(self.h0), ptr(self.sh), ptr(self.out), ptr(self.gout), ptr(self.eseg), E,
-                                           ptr(self.mws), ptr(self.dw), ptr(self.gh0), s), "acn_mlp_train_bwd_dw_pairs")
+        b.backward_mlp(self.h0, self.sh, self.out, self.gout, self.eseg, self.mws, self.gh0)
         check(L.acn_hashgrid_bwd_pairs_sumsq(ptr(self.x01), ptr(self.pkl), ptr(self.pflag), ptr(self.eseg), E,
-                                             ptr(self.gh0), self._gtables, self._res, len(enc._res_host),
-                                             enc.log2_hashmap_size, enc._interp_code,
+                                             ptr(self.gh0), b._gtables, *b.grid,
                                              ptr(self.table_sumsq) if self.tele else None, s),
               "acn_hashgrid_bwd_pairs_sumsq")
-        from . import routed_train as RT
         if bounded:   # an overflowed step activates no slot: no moment decay, no step count (seg[E] < 0)
             self.eseg[E:E + 1].copy_(torch.where(self.ovf > 0, torch.full_like(self.ovf, -1), self.eseg[E:E + 1]))
         self.adam.step(self.eseg, self.grad_clip, self.table_sumsq if self.tele else None,
@@ -1079,8 +983,6 @@ class ExpertParallelAdaptStep:
     def __call__(self, rays: Tensor, rgbs: Tensor, jitter_u: Optional[Tensor] = None) -> Tensor:
         """One update on this rank's ``rays`` / ``rgbs`` (n <= n_rays); collective over the group.  Returns the
         global loss (device, 1 element)."""
-        from ._lib import AcnError
-        from .optim import bump_versions
         n = int(rays.shape[0])
         if rays.dim() != 2 or rays.shape[1] != 8 or tuple(rgbs.shape) != (n, 3) or not 0 < n <= self.N:
             raise AcnError(f"ExpertParallelAdaptStep was built for up to {self.N} rays per rank; got "

@@ -22,6 +22,22 @@ from . import _lib
 from ._lib import ACN_OPTIM_CHUNK, ACN_OPTIM_MAX_GROUPS, AcnError, acn_adam_group, check, require_hip
 
 
+def pack_descs(items):
+    """Host image of a descriptor plan from (param, grad, exp_avg, exp_avg_sq, numel, key) integers per
+    tensor (addresses, 0 for no gradient): ((n, 6) int64 rows, int32 chunk -> tensor map, chunk count).
+    A row's last int64 is (first_chunk << 32) | key -- the bytes of acn_param_desc's trailing
+    {int32 group, int32 first_chunk} on the little-endian ABI (tests/test_optim_cpu.py)."""
+    descs, owners, first = [], [], 0
+    for t, (p, g, m, v, n, k) in enumerate(items):
+        nch = (n + ACN_OPTIM_CHUNK - 1) // ACN_OPTIM_CHUNK
+        descs.append([p, g, m, v, n, (first << 32) | k])
+        owners.append(torch.full((nch,), t, dtype=torch.int32))
+        first += nch
+    host = torch.tensor(descs, dtype=torch.int64) if descs else torch.zeros(0, 6, dtype=torch.int64)
+    own = torch.cat(owners) if owners else torch.zeros(0, dtype=torch.int32)
+    return host, own, first
+
+
 class _Plan:
     """Device descriptors (acn_param_desc) + chunk -> tensor map for a list of (p, g, m, v, key).
     Under stream capture the descriptors travel as kernel arguments (acn_optim_plan_device)."""
@@ -30,20 +46,14 @@ class _Plan:
         if torch.cuda.is_current_stream_capturing() and rows:
             self._init_captured(rows, device)
             return
-        self.key = tuple((p.data_ptr(), 0 if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr(), k)
-                         for p, g, m, v, k in rows)
-        descs, owners, first = [], [], 0
-        for t, (p, g, m, v, k) in enumerate(rows):
-            n = p.numel()
-            nch = (n + ACN_OPTIM_CHUNK - 1) // ACN_OPTIM_CHUNK
-            descs.append([p.data_ptr(), 0 if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr(), n,
-                          (first << 32) | k])
-            owners.append(torch.full((nch,), t, dtype=torch.int32))
-            first += nch
+        items = [(p.data_ptr(), 0 if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), k)
+                 for p, g, m, v, k in rows]
+        self.key = tuple(it[:4] + it[5:] for it in items)
+        host, own, first = pack_descs(items)
         self.nchunks = first
-        host = torch.tensor(descs, dtype=torch.int64).pin_memory() if descs else torch.zeros(0, 6, dtype=torch.int64)
+        if rows:
+            host = host.pin_memory()
         self.descs = host.to(device, non_blocking=True)
-        own = torch.cat(owners) if owners else torch.zeros(0, dtype=torch.int32)
         self.chunk_tensor = own.pin_memory().to(device, non_blocking=True) if own.numel() else own.to(device)
         self.partials = torch.empty(max(first, 1), dtype=torch.float64, device=device)
         self._keep = (host, own)
@@ -400,18 +410,12 @@ class SlottedAdam:
         dev = rows[0][0].device
         self.device = dev
         self.rows = rows
-        arr = (_lib.acn_param_desc * len(rows))()
-        first = 0
-        for t, (p, g, m, v, gi) in enumerate(rows):
-            arr[t] = _lib.acn_param_desc(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), gi, first)
-            first += (p.numel() + ACN_OPTIM_CHUNK - 1) // ACN_OPTIM_CHUNK
-        self.nchunks = first
-        self.descs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        self.chunk_tensor = torch.cat([torch.full(((r[0].numel() + ACN_OPTIM_CHUNK - 1) // ACN_OPTIM_CHUNK,), t,
-                                                  dtype=torch.int32) for t, r in enumerate(rows)]).to(dev)
+        plan = _Plan(rows, dev)
+        self.descs, self.chunk_tensor, self.nchunks, self.partials = (plan.descs, plan.chunk_tensor, plan.nchunks,
+                                                                      plan.partials)
+        self._plans = [plan]   # keeps the pinned host images of the asynchronous descriptor copies
         self.flags = torch.tensor(fl, device=dev, dtype=torch.int32)
         self._flags_host = list(fl)
-        self.partials = torch.empty(first, device=dev, dtype=torch.float64)
         self.total = torch.empty(1, device=dev, dtype=torch.float64)
         self.scale = torch.ones(2, device=dev, dtype=torch.float32)
         self.ticket = torch.zeros(1, device=dev, dtype=torch.int32)   # acn_grad_clip_slots' counter
@@ -442,18 +446,10 @@ class SlottedAdam:
         self.norm_plan = None
         keep = [t for t, f in enumerate(fl) if not f & NORM_ELSEWHERE_FLAG]
         if keep and len(keep) < len(rows):
-            arr = (_lib.acn_param_desc * len(keep))()
-            first = 0
-            for j, t in enumerate(keep):
-                p, g, m, v, gi = rows[t]
-                arr[j] = _lib.acn_param_desc(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), gi,
-                                             first)
-                first += (p.numel() + ACN_OPTIM_CHUNK - 1) // ACN_OPTIM_CHUNK
-            self.norm_plan = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev),
-                              torch.cat([torch.full(((rows[t][0].numel() + ACN_OPTIM_CHUNK - 1) // ACN_OPTIM_CHUNK,),
-                                                    j, dtype=torch.int32) for j, t in enumerate(keep)]).to(dev),
-                              first, torch.tensor([fl[t] for t in keep], device=dev, dtype=torch.int32),
-                              torch.empty(first, device=dev, dtype=torch.float64))
+            plan = _Plan([rows[t] for t in keep], dev)
+            self._plans.append(plan)
+            self.norm_plan = (plan.descs, plan.chunk_tensor, plan.nchunks,
+                              torch.tensor([fl[t] for t in keep], device=dev, dtype=torch.int32), plan.partials)
         # split_norm (expert parallel): the clip norm's sum of squares in two passes, the per-rank slots
         # (< K) first -- all-reduced over the group by the caller's function -- then the replicated shared
         # slots (>= K) once, added on top (the reference's clip_grad_norm_ over the whole container)
@@ -462,21 +458,17 @@ class SlottedAdam:
             own_flags = [f | (NORM_ELSEWHERE_FLAG if (f & 0xffff) >= self.K else 0) for f in fl]
             self.flags_own = torch.tensor(own_flags, device=dev, dtype=torch.int32)
             sh = [(r, f) for r, f in zip(rows, fl) if (f & 0xffff) >= self.K]
-            arr = (_lib.acn_param_desc * max(1, len(sh)))()
-            first = 0
-            for t, ((p, g, m, v, gi), f) in enumerate(sh):
-                arr[t] = _lib.acn_param_desc(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), gi,
-                                             first)
-                first += (p.numel() + ACN_OPTIM_CHUNK - 1) // ACN_OPTIM_CHUNK
-            if first == 0:
+            plan = _Plan([r for r, f in sh], dev)
+            if plan.nchunks == 0:
                 raise AcnError("SlottedAdam(split_norm): no shared parameter")
-            self.nchunks_sh = first
-            self.descs_sh = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-            self.chunk_sh = torch.cat([torch.full(((r[0].numel() + ACN_OPTIM_CHUNK - 1) // ACN_OPTIM_CHUNK,), t,
-                                                  dtype=torch.int32) for t, (r, f) in enumerate(sh)]).to(dev)
+            self._plans.append(plan)
+            self.descs_sh, self.chunk_sh, self.nchunks_sh, self.partials_sh = (plan.descs, plan.chunk_tensor,
+                                                                               plan.nchunks, plan.partials)
             self.flags_sh = torch.tensor([f & ~NORM_ELSEWHERE_FLAG for r, f in sh], device=dev, dtype=torch.int32)
-            self.partials_sh = torch.empty(first, device=dev, dtype=torch.float64)
             self.total_own = torch.empty(1, device=dev, dtype=torch.float64)
+        # _Plan's descriptor copies are asynchronous on the current stream: complete before any other stream
+        # (a side stream, a capture) launches on them
+        torch.cuda.current_stream(dev).synchronize()
 
     def _group_hparams(self):
         return tuple((float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"]))

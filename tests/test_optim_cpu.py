@@ -184,6 +184,32 @@ def test_clip_coef32_is_clip_grad_norm():
     assert math.isnan(R.clip_coef32(math.nan, 1.0)[1]) and float(R.clip_coef32(0.0, 1.0)[1]) == 1.0
 
 
+def test_packed_descriptor_rows_are_acn_param_desc_bytes():
+    """optim.pack_descs' six int64 per tensor, (first_chunk << 32) | group last, against the ctypes acn_param_desc
+    array and the torch.cat chunk -> tensor map SlottedAdam used to build by hand: one tensor of one element, one of
+    exactly a chunk, one a chunk and an element, one of several chunks with a partial last."""
+    import ctypes as C
+
+    from adaptive_city_nerf_amd import _lib
+    from adaptive_city_nerf_amd.optim import pack_descs
+    chunk = _lib.ACN_OPTIM_CHUNK
+    assert chunk == 65536 and C.sizeof(_lib.acn_param_desc) == 48
+    numels = [1, 65536, 65537, 200000]
+    items = [tuple(0x7f0000001000 + 0x10000000 * (4 * t + j) for j in range(4)) + (n, t) for t, n in enumerate(numels)]
+    assert len({a for it in items for a in it[:4]}) == 16
+    host, own, nchunks = pack_descs(items)
+    arr = (_lib.acn_param_desc * len(items))()
+    first = 0
+    for t, (p, g, m, v, n, gi) in enumerate(items):
+        arr[t] = _lib.acn_param_desc(p, g, m, v, n, gi, first)
+        first += (n + chunk - 1) // chunk
+    assert host.dtype == torch.int64 and tuple(host.shape) == (4, 6) and host.is_contiguous()
+    assert host.numpy().tobytes() == bytes(arr)
+    old_map = torch.cat([torch.full(((n + chunk - 1) // chunk,), t, dtype=torch.int32) for t, n in enumerate(numels)])
+    assert own.dtype == torch.int32 and torch.equal(own, old_map)
+    assert nchunks == first == 1 + 1 + 2 + 4 == own.numel()
+
+
 # ---------------------------------------------------------------------------------------------- planted mistakes
 SCENARIOS = {"plain": lambda: R.plain_scenario(30.0), "slotted": R.slotted_scenario, "segmap": R.segmap_scenario}
 # (scenario, mistake) pairs that cannot show, with the reason
