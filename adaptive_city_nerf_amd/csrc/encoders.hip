@@ -1249,9 +1249,14 @@ extern "C" int acn_hashgrid_pairs_mark(const float* x01, const int32_t* pk, cons
     for (int i = 0; i < L; ++i) r.v[i] = res[i];
     GradTables t{};
     SegMaps sm{};
+    // The kernel tells runs apart by their target address.  There are no gradient tables here, so expert k gets the
+    // address range a table of its own would have, k + 1 table sizes from 0: disjoint ranges, never null, and
+    // nothing is written through them.  (Derived from the maps' own addresses, rows of two experts whose maps lie
+    // closer than a table's size could share an address, and the second expert's segment went unmarked.)
+    const uint64_t table_bytes = ((uint64_t)L << log2T) * 2 * sizeof(float);
     for (int k = 0; k < K; ++k) {
         sm.t[k] = seg_now[k];
-        t.t[k] = reinterpret_cast<float*>(seg_now[k]);   // address arithmetic only: nothing is written through it
+        t.t[k] = reinterpret_cast<float*>((uintptr_t)((uint64_t)(k + 1) * table_bytes));
     }
     hipStream_t s = (hipStream_t)stream;
     if (interp == 1)
