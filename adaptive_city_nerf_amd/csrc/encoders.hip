@@ -5,6 +5,8 @@
 // directions.  One lane per (point, level): the L lanes of a
 // point are adjacent, so the (M, L*F) output row of a point is written as one contiguous
 // L*F*4-byte segment (128 B for the reference's L=16, F=2) and the point's x01 is a broadcast.
+#include <type_traits>
+
 #include "acn_device.h"
 #include "acn_internal.h"
 
@@ -13,6 +15,23 @@ namespace {
 struct Res32 {
     int32_t v[ACN_MAX_LEVELS];
 };
+
+// Smoothstep (INTERP == 2) replaces each lerp weight by S(w) = w^2 (3 - 2w); in this order, bit for bit
+template <int INTERP>
+__device__ __forceinline__ void smooth_weights(float& wx, float& wy, float& wz) {
+    if (INTERP == 2) {
+        wx = (wx * wx) * (3.0f - 2.0f * wx);
+        wy = (wy * wy) * (3.0f - 2.0f * wy);
+        wz = (wz * wz) * (3.0f - 2.0f * wz);
+    }
+}
+
+// The F == 2 gathers of tables up to 2 GiB go through one buffer resource over the whole table (32-bit offsets)
+inline bool table_fits_buffer(int L, int log2T) { return ((uint64_t)L << (log2T + 3)) <= (1ull << 31); }
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t table_rsrc(const float2* table, int L, int log2T) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)table, (short)0, (int)((uint32_t)L << (log2T + 3)), 0x00020000);
+}
 
 template <int INTERP>
 __global__ void __launch_bounds__(256) hashgrid_fwd_f2(const float* __restrict__ x01, int64_t M,
@@ -34,10 +53,8 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_f2(const float* __restrict__
 // Linear / Smoothstep through a buffer resource over the whole table (the renders' gather form):
 // 32-bit row offsets, and the x-neighbours of each (y, z) corner pair come from one 16-B block when x0 is even
 // (hash_issue_x: 4 dwordx4 gathers, plus 4 dwordx2 only for odd x0).  The same rows and the same lerp chain as
-// hash_level_f2, so the outputs are bitwise those of hashgrid_fwd_f2.  Tables up to 2 GiB (acn_hashgrid_fwd).
-#ifndef ACN_HASH_FWD_BUF
-#define ACN_HASH_FWD_BUF 1
-#endif
+// hash_level_f2, so the outputs are bitwise those of hashgrid_fwd_f2.  Tables up to 2 GiB (table_fits_buffer);
+// hashgrid_fwd_f2 serves Nearest and the larger tables.
 template <int INTERP>
 __global__ void __launch_bounds__(256) hashgrid_fwd_f2_buf(const float* __restrict__ x01, int64_t M,
                                                            const float2* __restrict__ table, Res32 res, int L,
@@ -49,8 +66,7 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_f2_buf(const float* __restri
     const float r = (float)res.v[l];
     const float sx = x01[3 * m] * r, sy = x01[3 * m + 1] * r, sz = x01[3 * m + 2] * r;
     const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)table, (short)0, (int)((uint32_t)L << (log2T + 3)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = table_rsrc(table, L, log2T);
     acn::HashPendingX p;
     acn::hash_issue_x<INTERP>(rs, (uint32_t)l << (log2T + 3), sx, sy, sz, mask, p);
     float o0, o1;
@@ -80,11 +96,7 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_gen(const float* __restrict_
     }
     const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
     float wx = sx - fx, wy = sy - fy, wz = sz - fz;
-    if (INTERP == 2) {
-        wx = (wx * wx) * (3.0f - 2.0f * wx);
-        wy = (wy * wy) * (3.0f - 2.0f * wy);
-        wz = (wz * wz) * (3.0f - 2.0f * wz);
-    }
+    smooth_weights<INTERP>(wx, wy, wz);
     const uint32_t x0 = (uint32_t)(int)fx, x1 = x0 + 1u;
     const uint32_t y0 = (uint32_t)(int)fy * acn::kP1, y1 = y0 + acn::kP1;
     const uint32_t z0 = (uint32_t)(int)fz * acn::kP2, z1 = z0 + acn::kP2;
@@ -133,11 +145,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_gen(const float* __restrict_
     }
     const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
     float wx = sx - fx, wy = sy - fy, wz = sz - fz;
-    if (INTERP == 2) {
-        wx = (wx * wx) * (3.0f - 2.0f * wx);
-        wy = (wy * wy) * (3.0f - 2.0f * wy);
-        wz = (wz * wz) * (3.0f - 2.0f * wz);
-    }
+    smooth_weights<INTERP>(wx, wy, wz);
     const float ax = 1.0f - wx, ay = 1.0f - wy, az = 1.0f - wz;
     const uint32_t x0 = (uint32_t)(int)fx;
     const uint32_t y0 = (uint32_t)(int)fy * acn::kP1;
@@ -154,49 +162,53 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_gen(const float* __restrict_
     }
 }
 
-// F == 2, Linear/Smoothstep: one lane per (point, level, corner, feature).  A wave covers 4
-// consecutive points at ONE level, lanes ordered (point, y/z corner, x corner, feature), so each
-// no-return atomic instruction touches ~16 table row pairs (the x-neighbours of a corner pair
-// share a 128-B line) instead of the 64 unrelated rows of the lane-per-(point, level) mapping
-// (MI355X_MICROARCH.md "Global float atomics": rate set by distinct rows per instruction).  The
-// per-corner gradient keeps the forward's chain-rule order ((g * wz) * wy) * wx.
+// ---------------------------------------------------------------------------------------------
+// F == 2, Linear / Smoothstep table scatters: one lane per (point stream, corner, feature).  The 64 lanes of a wave
+// are 4 streams x 8 corners x 2 features at ONE level, ordered (stream, y/z corner, x corner, feature), so each
+// no-return atomic instruction touches ~16 table row pairs (the x-neighbours of a corner pair share a 128-B line)
+// instead of the 64 unrelated rows of a lane-per-(point, level) mapping (MI355X_MICROARCH.md "Global float
+// atomics": rate set by distinct rows per instruction).
+struct CornerLane {
+    int f, bx, by, bz;   // feature; the corner's bit per axis
+    __device__ explicit CornerLane(int lane)
+        : f(lane & 1), bx((lane >> 1) & 1), by((lane >> 3) & 1), bz((lane >> 2) & 1) {}
+    // the hashed row of this corner of the cell whose floor is (fx, fy, fz)
+    __device__ __forceinline__ uint32_t row(float fx, float fy, float fz, uint32_t mask) const {
+        const uint32_t xi = (uint32_t)(int)fx + (uint32_t)bx;
+        const uint32_t yi = (uint32_t)(int)fy * acn::kP1 + (by ? acn::kP1 : 0u);
+        const uint32_t zi = (uint32_t)(int)fz * acn::kP2 + (bz ? acn::kP2 : 0u);
+        return (xi ^ yi ^ zi) & mask;
+    }
+};
+struct Corner {
+    uint32_t row;
+    float wx, wy, wz;   // the corner's weight per axis: w or 1 - w
+};
+
+// The corner of lane c for point m at a level of resolution r.  Its table gradient is ((g * wz) * wy) * wx, the
+// chain-rule order of the forward lerps: every scatter forms it in exactly that order (the file is built with
+// -ffp-contract=off, so the kernels agree bit for bit).  The complement is 1 - w of the SMOOTHED
+// weight, as in the forward; axis_w (the double backward) takes S(1 - u) instead and must not be used here.
 template <int INTERP>
-__global__ void __launch_bounds__(256) hashgrid_bwd_f2(const float* __restrict__ x01, int64_t M,
-                                                       const float* __restrict__ gout, Res32 res, int L,
-                                                       int log2T, float* __restrict__ gtable) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t groups = (M + 3) >> 2;               // groups of 4 points
-    const int l = (int)(wave / groups);
-    const int64_t m = (wave - (int64_t)l * groups) * 4 + (lane >> 4);
-    if (l >= L || m >= M) return;
-    const int f = lane & 1, bx = (lane >> 1) & 1, by = (lane >> 3) & 1, bz = (lane >> 2) & 1;
-    const float r = (float)res.v[l];
+__device__ __forceinline__ Corner lane_corner(const CornerLane& c, const float* __restrict__ x01, int64_t m, float r,
+                                              uint32_t mask) {
     const float sx = x01[3 * m] * r, sy = x01[3 * m + 1] * r, sz = x01[3 * m + 2] * r;
-    const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
     const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
     float wx = sx - fx, wy = sy - fy, wz = sz - fz;
-    if (INTERP == 2) {
-        wx = (wx * wx) * (3.0f - 2.0f * wx);
-        wy = (wy * wy) * (3.0f - 2.0f * wy);
-        wz = (wz * wz) * (3.0f - 2.0f * wz);
-    }
-    const uint32_t xi = (uint32_t)(int)fx + (uint32_t)bx;
-    const uint32_t yi = (uint32_t)(int)fy * acn::kP1 + (by ? acn::kP1 : 0u);
-    const uint32_t zi = (uint32_t)(int)fz * acn::kP2 + (bz ? acn::kP2 : 0u);
-    const uint32_t h = (xi ^ yi ^ zi) & mask;
-    const float gv = ((gout[(m * L + l) * 2 + f] * (bz ? wz : 1.0f - wz)) * (by ? wy : 1.0f - wy)) * (bx ? wx : 1.0f - wx);
-    unsafeAtomicAdd(gtable + (((int64_t)l << log2T) + h) * 2 + f, gv);
+    smooth_weights<INTERP>(wx, wy, wz);
+    return Corner{c.row(fx, fy, fz, mask), c.bx ? wx : 1.0f - wx, c.by ? wy : 1.0f - wy, c.bz ? wz : 1.0f - wz};
 }
 
-// Run-length-aggregated variant: lane = (sub-group s = lane >> 4, corner, feature) walks PPL
-// consecutive points (a stretch of one ray: the training path lays samples out ray-major) at one
-// level, summing gradients in a register while the target row repeats and issuing one atomic per
-// run.  Coarse levels see long runs (several samples per cell), which is where the per-row atomic
-// contention was; waves interleave levels (l = wave % L) so concurrent waves spread over all levels
-// instead of all hammering level 0's few thousand rows at once.  Sum order within a run is the
-// sample order; across runs it is the (unordered) atomic order, as before.
-template <int INTERP, int PPL>
+// consecutive points per lane in hashgrid_bwd_rle / hashgrid_bwd_pairs
+constexpr int kRunPoints = 16;
+
+// Run-length-aggregated scatter: a lane walks kRunPoints consecutive points of its stream (a stretch of one ray:
+// the training path lays samples out ray-major) at one level, summing gradients in a register while the target
+// row repeats and issuing one atomic per run.  Coarse levels see long runs (several samples per cell), which is
+// where the per-row atomic contention was; waves interleave levels (l = wave % L) so concurrent waves spread over
+// all levels instead of all hammering level 0's few thousand rows at once.  Sum order within a run is the sample
+// order; across runs it is the (unordered) atomic order.
+template <int INTERP>
 __global__ void __launch_bounds__(256) hashgrid_bwd_rle(const float* __restrict__ x01, int64_t M,
                                                         const float* __restrict__ gout, Res32 res, int L,
                                                         int log2T, float* __restrict__ gtable, int l0) {
@@ -204,32 +216,21 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_rle(const float* __restrict_
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int l = l0 + (int)(wave % (L - l0));  // levels l0..L-1 (the coarser ones: hashgrid_bwd_merge)
     const int64_t chunk = wave / (L - l0);
-    const int64_t m0 = (chunk * 4 + (lane >> 4)) * PPL;
+    const int64_t m0 = (chunk * 4 + (lane >> 4)) * kRunPoints;
     if (m0 >= M) return;
-    const int f = lane & 1, bx = (lane >> 1) & 1, by = (lane >> 3) & 1, bz = (lane >> 2) & 1;
+    const CornerLane c(lane);
     const float r = (float)res.v[l];
     const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
-    const int64_t base = ((int64_t)l << log2T) * 2 + f;
+    const int64_t base = ((int64_t)l << log2T) * 2 + c.f;
     int64_t cur = -1;
     float acc = 0.0f;
 #pragma unroll 4
-    for (int i = 0; i < PPL; ++i) {
+    for (int i = 0; i < kRunPoints; ++i) {
         const int64_t m = m0 + i;
         if (m >= M) break;
-        const float sx = x01[3 * m] * r, sy = x01[3 * m + 1] * r, sz = x01[3 * m + 2] * r;
-        const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
-        float wx = sx - fx, wy = sy - fy, wz = sz - fz;
-        if (INTERP == 2) {
-            wx = (wx * wx) * (3.0f - 2.0f * wx);
-            wy = (wy * wy) * (3.0f - 2.0f * wy);
-            wz = (wz * wz) * (3.0f - 2.0f * wz);
-        }
-        const uint32_t xi = (uint32_t)(int)fx + (uint32_t)bx;
-        const uint32_t yi = (uint32_t)(int)fy * acn::kP1 + (by ? acn::kP1 : 0u);
-        const uint32_t zi = (uint32_t)(int)fz * acn::kP2 + (bz ? acn::kP2 : 0u);
-        const int64_t a = base + (int64_t)((xi ^ yi ^ zi) & mask) * 2;
-        const float gv = ((gout[(m * L + l) * 2 + f] * (bz ? wz : 1.0f - wz)) * (by ? wy : 1.0f - wy)) *
-                         (bx ? wx : 1.0f - wx);
+        const Corner k = lane_corner<INTERP>(c, x01, m, r, mask);
+        const int64_t a = base + (int64_t)k.row * 2;
+        const float gv = ((gout[(m * L + l) * 2 + c.f] * k.wz) * k.wy) * k.wx;
         if (a == cur) {
             acc += gv;
         } else {
@@ -240,10 +241,6 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_rle(const float* __restrict_
     }
     if (cur >= 0) unsafeAtomicAdd(gtable + cur, acc);
 }
-
-#ifndef ACN_HASH_BWD_PPL
-#define ACN_HASH_BWD_PPL 16  // consecutive points per lane in hashgrid_bwd_rle (0: the per-point kernel)
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // (sample, expert) pair lists of the routed container (routed.hip): slot p belongs to expert pk[p],
@@ -277,8 +274,7 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_pairs(const float* __restric
             for (;;) {
                 const int kw = __builtin_amdgcn_readfirstlane(k);
                 if (k == kw) {
-                    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                        (void*)tabs.t[kw], (short)0, (int)((uint32_t)L << (log2T + 3)), 0x00020000);
+                    const __amdgpu_buffer_rsrc_t rs = table_rsrc(tabs.t[kw], L, log2T);
                     acn::HashPendingX p;
                     acn::hash_issue_x<INTERP>(rs, (uint32_t)l << (log2T + 3), sx, sy, sz, mask, p);
                     acn::hash_finish_x<INTERP>(p, o0, o1);
@@ -293,24 +289,23 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_pairs(const float* __restric
     }
 }
 
-// hashgrid_bwd_rle over pair slots: the run key is the target address, so a stretch may cross an
-// expert boundary; padding slots (pidx < 0) add nothing
+// hashgrid_bwd_rle over pair slots: the run key is (expert, row), so a stretch may cross an expert
+// boundary; padding slots (pidx < 0) add nothing.  MARK_ONLY (acn_hashgrid_pairs_mark) reads neither gout nor gt.
 // TELE: returning atomics; every run adds new^2 - old^2 (new = old + run sum, the value the atomic
 // leaves) to *sq.  Per row these telescope to (final value)^2 - 0, so *sq gains the squared norm of the
 // table-gradient update without a pass over the 128 MiB gradient buffers (clip_grad_norm_'s sum of
 // squares, runtime_adapt.py:305-307).  Doubles: new^2 and old^2 are exact, so only the differences and
 // their sum round (~1e-16 relative).
-template <int INTERP, int PPL, bool TELE, bool MARK_ONLY = false>
+template <int INTERP, bool TELE, bool MARK_ONLY = false>
 __global__ void __launch_bounds__(256) hashgrid_bwd_pairs(const float* __restrict__ x01, const int32_t* __restrict__ pk,
                                                           const int32_t* __restrict__ pidx,
                                                           const int64_t* __restrict__ seg, int K,
                                                           const float* __restrict__ gout, GradTables gt, Res32 res,
-                                                          int L, int log2T, int l0, double* __restrict__ sq,
-                                                          SegMaps smaps) {
+                                                          int L, int log2T, double* __restrict__ sq, SegMaps smaps) {
     const int lane = threadIdx.x & 63;
     const int64_t M = seg[K];
-    const int64_t nwaves = ((M + 4 * PPL - 1) / (4 * PPL)) * (L - l0);
-    const int f = lane & 1, bx = (lane >> 1) & 1, by = (lane >> 3) & 1, bz = (lane >> 2) & 1;
+    const int64_t nwaves = ((M + 4 * kRunPoints - 1) / (4 * kRunPoints)) * L;
+    const CornerLane c(lane);
     const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
     double tsq = 0.0;
     auto flush = [&](float* a, float v) {
@@ -325,50 +320,39 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_pairs(const float* __restric
     };
     for (int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; wave < nwaves;
          wave += ((int64_t)gridDim.x * blockDim.x) >> 6) {
-        const int l = l0 + (int)(wave % (L - l0));
-        const int64_t chunk = wave / (L - l0);
-        const int64_t m0 = (chunk * 4 + (lane >> 4)) * PPL;
+        const int l = (int)(wave % L);
+        const int64_t chunk = wave / L;
+        const int64_t m0 = (chunk * 4 + (lane >> 4)) * kRunPoints;
         const float r = (float)res.v[l];
-        const int64_t base = ((int64_t)l << log2T) * 2 + f;
-        float* cur = nullptr;
-        uint8_t* cseg = nullptr;   // the segment-map byte of cur's 64-B segment (segment maps on)
+        const int64_t base = ((int64_t)l << log2T) * 2 + c.f;
+        constexpr uint32_t kNoRun = 0xffffffffu;   // rows have at most 30 bits
+        uint32_t cur_row = kNoRun;
+        int cur_k = 0;
+        uint8_t* cseg = nullptr;   // the segment-map byte of the run's 64-B segment (segment maps on)
         float acc = 0.0f;
-        for (int i = 0; i < PPL; ++i) {
+        auto end_run = [&]() {
+            if (cur_row == kNoRun) return;
+            flush(gt.t[cur_k] + base + (int64_t)cur_row * 2, acc);
+            if (cseg && c.f == 0) *cseg = 1;   // idempotent plain byte store (feature 1 shares the row)
+        };
+        for (int i = 0; i < kRunPoints; ++i) {
             const int64_t m = m0 + i;
             if (m >= M) break;
             if (pidx[m] < 0) continue;
-            const float sx = x01[3 * m] * r, sy = x01[3 * m + 1] * r, sz = x01[3 * m + 2] * r;
-            const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
-            float wx = sx - fx, wy = sy - fy, wz = sz - fz;
-            if (INTERP == 2) {
-                wx = (wx * wx) * (3.0f - 2.0f * wx);
-                wy = (wy * wy) * (3.0f - 2.0f * wy);
-                wz = (wz * wz) * (3.0f - 2.0f * wz);
-            }
-            const uint32_t xi = (uint32_t)(int)fx + (uint32_t)bx;
-            const uint32_t yi = (uint32_t)(int)fy * acn::kP1 + (by ? acn::kP1 : 0u);
-            const uint32_t zi = (uint32_t)(int)fz * acn::kP2 + (bz ? acn::kP2 : 0u);
+            const Corner k = lane_corner<INTERP>(c, x01, m, r, mask);
             const int kk = pk[m];
-            const uint32_t row = (xi ^ yi ^ zi) & mask;
-            float* a = gt.t[kk] + base + (int64_t)row * 2;
-            const float gv = MARK_ONLY ? 0.0f : ((gout[(m * L + l) * 2 + f] * (bz ? wz : 1.0f - wz)) *
-                                                 (by ? wy : 1.0f - wy)) * (bx ? wx : 1.0f - wx);
-            if (a == cur) {
+            const float gv = MARK_ONLY ? 0.0f : ((gout[(m * L + l) * 2 + c.f] * k.wz) * k.wy) * k.wx;
+            if (k.row == cur_row && kk == cur_k) {
                 acc += gv;
             } else {
-                if (cur) {
-                    flush(cur, acc);
-                    if (cseg && f == 0) *cseg = 1;   // idempotent plain byte store (feature 1 shares the row)
-                }
-                cur = a;
-                cseg = smaps.t[kk] ? smaps.t[kk] + ((((int64_t)l << log2T) + row) >> 3) : nullptr;
+                end_run();
+                cur_row = k.row;
+                cur_k = kk;
+                cseg = smaps.t[kk] ? smaps.t[kk] + ((((int64_t)l << log2T) + k.row) >> 3) : nullptr;
                 acc = gv;
             }
         }
-        if (cur) {
-            flush(cur, acc);
-            if (cseg && f == 0) *cseg = 1;
-        }
+        end_run();
     }
     if (TELE) {  // one double atomic per wave
 #pragma unroll
@@ -378,31 +362,36 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_pairs(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// Coarse levels of the table-gradient scatter, merged per workgroup.  At the coarse
-// levels many samples -- of one ray and of neighbouring rays -- add into the same rows, but a lane's run
-// merge only sees one corner of one sample stream.  Here a workgroup takes a chunk of C_l consecutive
-// slots at one level, accumulates every (slot, corner) contribution into an LDS hash table keyed by
-// (table, 64-B segment) with LDS float atomics, then flushes each touched segment as 16 consecutive
-// floats (4 segments per wave-instruction = the full-rate shape of MI355X_MICROARCH.md 'Global float
-// atomics').  Memory-side requests fall from one per (run, corner pair) to one per distinct segment of
-// the chunk.  A full table (more distinct segments than kMergeNE) falls back to direct atomics for the
-// overflowing contributions.  Sums stay fp32; their order is as unordered as the atomics they replace.
+// Coarse levels of the standalone table-gradient scatter (acn_hashgrid_bwd), merged per workgroup.
+// At the coarse levels many samples -- of one ray and of neighbouring rays -- add into the same rows, but a lane's
+// run merge only sees one corner of one sample stream.  Here a workgroup takes a chunk of C_l consecutive points at
+// one level, accumulates every (point, corner) contribution into an LDS hash table keyed by the row's 64-B
+// segment with LDS float atomics, then flushes each touched segment as 16 consecutive floats (4 segments per
+// wave-instruction = the full-rate shape of MI355X_MICROARCH.md 'Global float atomics').  Memory-side requests fall
+// from one per (run, corner pair) to one per distinct segment of the chunk.  A full table (more distinct segments
+// than kMergeNE) falls back to direct atomics for the overflowing contributions.  Sums stay fp32; their order is as
+// unordered as the atomics they replace.
+// The pair-list scatter (hashgrid_bwd_pairs) keeps every level on the run merge: merged coarse levels measured
+// slower on the C5 step (hash backward 0.36 -> 0.76 / 0.79 / 0.89 ms merging 3 / 6 / 8 levels) -- a
+// coarse chunk is one workgroup's serial work (few items in flight) and the runs of neighbouring lanes collide on
+// the same LDS entries -- and they can neither telescope the clip norm nor mark the segment maps.
 constexpr int kMergeLogNE = 10, kMergeNE = 1 << kMergeLogNE;
 constexpr uint32_t kMergeEmpty = 0xffffffffu;
+// merged levels of the standalone scatter (the meta-training query step, whose batch is ~6x C5's): 6 cut the
+// scatter 855 -> 795 us and the meta step 1.1%
+constexpr int kMergeLevels = 6;
 struct MergeCfg {
     int LM;                   // levels 0 .. LM-1 are merged here
-    int clog2[ACN_MAX_LEVELS];  // chunk of 2^clog2[l] slots per workgroup item at level l
+    int clog2[ACN_MAX_LEVELS];  // chunk of 2^clog2[l] points per workgroup item at level l
 };
 
 template <int INTERP>
-__global__ void __launch_bounds__(256) hashgrid_bwd_merge(const float* __restrict__ x01, const int32_t* __restrict__ pk,
-                                                          const int32_t* __restrict__ pidx,
-                                                          const int64_t* __restrict__ seg, int K, int64_t Mhost,
-                                                          const float* __restrict__ gout, GradTables gt, Res32 res,
-                                                          int L, int log2T, MergeCfg cfg) {
+__global__ void __launch_bounds__(256) hashgrid_bwd_merge(const float* __restrict__ x01, int64_t M,
+                                                          const float* __restrict__ gout,
+                                                          float* __restrict__ gtable, Res32 res, int L, int log2T,
+                                                          MergeCfg cfg) {
     __shared__ uint32_t keys[kMergeNE];
     __shared__ __attribute__((aligned(16))) float vals[kMergeNE * 16];
-    const int64_t M = seg ? seg[K] : Mhost;
     int64_t items = 0;
     for (int l = 0; l < cfg.LM; ++l) items += (M + (1ll << cfg.clog2[l]) - 1) >> cfg.clog2[l];
     const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
@@ -420,86 +409,57 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_merge(const float* __restric
             reinterpret_cast<float4*>(vals)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         __syncthreads();
         const float r = (float)res.v[l];
-        // lanes as in hashgrid_bwd_rle: (stream q, corner, feature f); a lane run-merges 16 consecutive
-        // slots of its stream and adds each finished run into the LDS table (LDS atomics on runs, not on
-        // every contribution: coarse cells repeat along a ray)
+        float* tl = gtable + ((int64_t)l << log2T) * 2;
+        // lanes as in hashgrid_bwd_rle; a lane run-merges 16 consecutive points of its stream and adds each
+        // finished run into the LDS table (LDS atomics on runs, not on every contribution: coarse cells repeat
+        // along a ray)
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-        const int f = lane & 1, bx = (lane >> 1) & 1, by = (lane >> 3) & 1, bz = (lane >> 2) & 1;
-        auto add_run = [&](uint32_t kx, uint32_t row, float v) {
-            const uint32_t key = (kx << 24) | (row >> 3);
+        const CornerLane c(lane);
+        auto add_run = [&](uint32_t row, float v) {
+            const uint32_t key = row >> 3;   // the row's 64-B segment: 24 bits (merge_cfg), never kMergeEmpty
             uint32_t h = (key * 2654435761u) >> (32 - kMergeLogNE);
             for (int probe = 0; probe < 32; ++probe) {
                 uint32_t cur = keys[h];
                 if (cur == kMergeEmpty) cur = atomicCAS(&keys[h], kMergeEmpty, key);
                 if (cur == kMergeEmpty || cur == key) {
-                    atomicAdd(&vals[h * 16 + (row & 7) * 2 + f], v);
+                    atomicAdd(&vals[h * 16 + (row & 7) * 2 + c.f], v);
                     return;
                 }
                 h = (h + 1) & (kMergeNE - 1);
             }
-            unsafeAtomicAdd(gt.t[kx] + (((int64_t)l << log2T) + row) * 2 + f, v);  // table crowded
+            unsafeAtomicAdd(tl + (int64_t)row * 2 + c.f, v);  // table crowded
         };
         for (int64_t sb = m0 + (int64_t)w * 64; sb < m1; sb += (int64_t)nw * 64) {
             const int64_t mb = sb + (lane >> 4) * 16;
-            uint32_t cur_row = 0xffffffffu, cur_k = 0;
+            uint32_t cur_row = 0xffffffffu;
             float acc = 0.0f;
             for (int i = 0; i < 16; ++i) {
                 const int64_t m = mb + i;
                 if (m >= m1) break;
-                if (pidx && pidx[m] < 0) continue;
-                const uint32_t kx = pk ? (uint32_t)pk[m] : 0u;
-                const float sx = x01[3 * m] * r, sy = x01[3 * m + 1] * r, sz = x01[3 * m + 2] * r;
-                const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
-                float wx = sx - fx, wy = sy - fy, wz = sz - fz;
-                if (INTERP == 2) {
-                    wx = (wx * wx) * (3.0f - 2.0f * wx);
-                    wy = (wy * wy) * (3.0f - 2.0f * wy);
-                    wz = (wz * wz) * (3.0f - 2.0f * wz);
-                }
-                const uint32_t xi = (uint32_t)(int)fx + (uint32_t)bx;
-                const uint32_t yi = (uint32_t)(int)fy * acn::kP1 + (by ? acn::kP1 : 0u);
-                const uint32_t zi = (uint32_t)(int)fz * acn::kP2 + (bz ? acn::kP2 : 0u);
-                const uint32_t row = (xi ^ yi ^ zi) & mask;
-                const float gv = ((gout[(m * L + l) * 2 + f] * (bz ? wz : 1.0f - wz)) * (by ? wy : 1.0f - wy)) *
-                                 (bx ? wx : 1.0f - wx);
-                if (row == cur_row && kx == cur_k) {
+                const Corner k = lane_corner<INTERP>(c, x01, m, r, mask);
+                const float gv = ((gout[(m * L + l) * 2 + c.f] * k.wz) * k.wy) * k.wx;
+                if (k.row == cur_row) {
                     acc += gv;
                 } else {
-                    if (cur_row != 0xffffffffu) add_run(cur_k, cur_row, acc);
-                    cur_row = row;
-                    cur_k = kx;
+                    if (cur_row != 0xffffffffu) add_run(cur_row, acc);
+                    cur_row = k.row;
                     acc = gv;
                 }
             }
-            if (cur_row != 0xffffffffu) add_run(cur_k, cur_row, acc);
+            if (cur_row != 0xffffffffu) add_run(cur_row, acc);
         }
         __syncthreads();
         // flush: 16 consecutive lanes per segment
         for (int i = threadIdx.x; i < kMergeNE * 16; i += blockDim.x) {
             const uint32_t key = keys[i >> 4];
             const float v = vals[i];
-            if (key != kMergeEmpty && v != 0.0f)
-                unsafeAtomicAdd(gt.t[key >> 24] + ((int64_t)l << log2T) * 2 + (int64_t)(key & 0xffffffu) * 16 + (i & 15), v);
+            if (key != kMergeEmpty && v != 0.0f) unsafeAtomicAdd(tl + (int64_t)key * 16 + (i & 15), v);
         }
         __syncthreads();
     }
 }
 
-#ifndef ACN_HASH_BWD_MERGE
-// coarse levels merged per workgroup in the pair-list scatter (C5; 0: every level on the run-merge kernel).  Off:
-// measured slower on the C5 step (hash backward 0.36 -> 0.76 / 0.79 / 0.89 ms merging 3 / 6 / 8 levels,
-// tools/ab_c5.sh) -- a coarse chunk is one workgroup's serial work (few items in flight), and the
-// runs of neighbouring lanes collide on the same LDS entries; it also cannot telescope the clip norm or mark the
-// segment maps the C5 step needs
-#define ACN_HASH_BWD_MERGE 0
-#endif
-#ifndef ACN_HASH_BWD_MERGE_SA
-// the same for the standalone scatter (acn_hashgrid_bwd: the meta-training query step, whose batch is ~6x C5's):
-// 6 merged levels there cut the scatter 855 -> 795 us and the meta step 1.1%
-#define ACN_HASH_BWD_MERGE_SA 6
-#endif
-
-MergeCfg merge_cfg(int L, int log2T, int levels = ACN_HASH_BWD_MERGE) {
+MergeCfg merge_cfg(int L, int log2T, int levels) {
     MergeCfg c{};
     c.LM = levels < L ? levels : L;
     if (log2T > 27) c.LM = 0;  // the LDS key holds a 24-bit segment index
@@ -550,8 +510,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_input_f2(const float* __rest
                                                              const float2* __restrict__ table, Res32 res, int L,
                                                              int log2T, float* __restrict__ gx) {
     const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)table, (short)0, (int)((uint32_t)L << (log2T + 3)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = table_rsrc(table, L, log2T);
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (TREE) {
         // L is a power of two <= 32: a point's lanes are one aligned group of a wave, live or idle together
@@ -738,8 +697,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_input_bwd_f2(const float* __
                                                                  int log2T, float2* __restrict__ ggout,
                                                                  float* __restrict__ gx2) {
     const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)table, (short)0, (int)((uint32_t)L << (log2T + 3)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = table_rsrc(table, L, log2T);
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool want_gg = ggout != nullptr, want_gx = gx2 != nullptr;
     if (TREE) {
@@ -846,8 +804,9 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_input_bwd_gen(const float* _
     }
 }
 
-// The table side, F == 2: hashgrid_bwd_f2's lane mapping (4 points x 8 corners x 2 features per wave at one level),
-// k_b in place of the trilinear weight.
+// The table side, F == 2: one lane per (point, corner, feature), no run merge.  A wave is 4 consecutive points x
+// CornerLane's 8 corners x 2 features at one level; waves go level by level over the groups of 4 points.  k_b in
+// place of the trilinear weight (its weights are axis_w's, not lane_corner's).
 template <int INTERP>
 __global__ void __launch_bounds__(256) hashgrid_bwd_input_bwd_table_f2(const float* __restrict__ x01, int64_t M,
                                                                        const float* __restrict__ gout,
@@ -859,20 +818,16 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_input_bwd_table_f2(const flo
     const int l = (int)(wave / groups);
     const int64_t m = (wave - (int64_t)l * groups) * 4 + (lane >> 4);
     if (l >= L || m >= M) return;
-    const int f = lane & 1;
-    const bool bx = ((lane >> 1) & 1) != 0, by = ((lane >> 3) & 1) != 0, bz = ((lane >> 2) & 1) != 0;
+    const CornerLane c(lane);
     const float r = (float)res.v[l];
     const float sx = x01[3 * m] * r, sy = x01[3 * m + 1] * r, sz = x01[3 * m + 2] * r;
     const uint32_t mask = (uint32_t)((1ull << log2T) - 1ull);
     const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
     const AxisW X = axis_w<INTERP>(sx - fx), Y = axis_w<INTERP>(sy - fy), Z = axis_w<INTERP>(sz - fz);
-    const uint32_t xi = (uint32_t)(int)fx + (bx ? 1u : 0u);
-    const uint32_t yi = (uint32_t)(int)fy * acn::kP1 + (by ? acn::kP1 : 0u);
-    const uint32_t zi = (uint32_t)(int)fz * acn::kP2 + (bz ? acn::kP2 : 0u);
-    const uint32_t h = (xi ^ yi ^ zi) & mask;
+    const uint32_t h = c.row(fx, fy, fz, mask);
     const float k = corner_k((ggx[3 * m] * r) * X.d1, (ggx[3 * m + 1] * r) * Y.d1, (ggx[3 * m + 2] * r) * Z.d1,
-                             bx ? X.w : X.a, by ? Y.w : Y.a, bz ? Z.w : Z.a, bx, by, bz);
-    unsafeAtomicAdd(gtable + (((int64_t)l << log2T) + h) * 2 + f, k * gout[(m * L + l) * 2 + f]);
+                             c.bx ? X.w : X.a, c.by ? Y.w : Y.a, c.bz ? Z.w : Z.a, c.bx, c.by, c.bz);
+    unsafeAtomicAdd(gtable + (((int64_t)l << log2T) + h) * 2 + c.f, k * gout[(m * L + l) * 2 + c.f]);
 }
 
 // generic F: hashgrid_bwd_gen's mapping, one lane per (point, level)
@@ -951,83 +906,105 @@ __global__ void __launch_bounds__(256) sh_fwd_kernel(const float* __restrict__ d
     for (int i = 0; i < C; ++i) out[m * C + i] = c[i];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side.  The runtime interpolation mode (and a flag) become template arguments through generic lambdas:
+// with_interp(interp, [&](auto i) { constexpr int I = decltype(i)::value; ... kernel<I> ... }).
+template <class Fn>
+void with_lerp(int interp, Fn&& fn) {   // Linear / Smoothstep: the caller has handled or rejected Nearest
+    if (interp == 1) fn(std::integral_constant<int, 1>{});
+    else fn(std::integral_constant<int, 2>{});
+}
+template <class Fn>
+void with_interp(int interp, Fn&& fn) {
+    if (interp == 0) fn(std::integral_constant<int, 0>{});
+    else with_lerp(interp, fn);
+}
+template <class Fn>
+void with_bool(bool b, Fn&& fn) {
+    if (b) fn(std::true_type{});
+    else fn(std::false_type{});
+}
+
+inline dim3 blocks(int64_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
+
+Res32 pack_res(const int32_t* res, int L) {
+    Res32 r{};
+    for (int i = 0; i < L; ++i) r.v[i] = res[i];
+    return r;
+}
+
+// The arguments common to the grid entry points, reported under the entry point's name fn; packs res into r.
+// fmax: the entry's cap on features_per_level, 0 for none (the input-gradient entries take any F >= 1).
+int check_grid(const char* fn, int64_t M, int L, int log2T, int F, int fmax, int interp, const int32_t* res,
+               Res32& r) {
+    ACN_REQUIRE(M >= 0, "%s: M must be >= 0", fn);
+    ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS, "%s: levels must be in [1, %d], got %d", fn, ACN_MAX_LEVELS, L);
+    ACN_REQUIRE(log2T >= 1 && log2T <= 30, "%s: log2_hashmap_size must be in [1, 30], got %d", fn, log2T);
+    if (fmax) ACN_REQUIRE(F >= 1 && F <= fmax, "%s: features_per_level must be in [1, %d], got %d", fn, fmax, F);
+    else ACN_REQUIRE(F >= 1, "%s: features_per_level must be >= 1, got %d", fn, F);
+    ACN_REQUIRE(interp >= 0 && interp <= 2, "%s: bad interpolation %d", fn, interp);
+    ACN_REQUIRE(res != nullptr, "%s: res is NULL", fn);
+    r = pack_res(res, L);
+    return ACN_OK;
+}
+
 }  // namespace
 
 extern "C" int acn_hashgrid_fwd(const float* x01, int64_t M, const float* table, const int32_t* res, int L,
                                 int log2T, int F, int interp, float* out, void* stream) {
-    ACN_REQUIRE(M >= 0, "acn_hashgrid_fwd: M must be >= 0");
-    ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS, "acn_hashgrid_fwd: levels must be in [1, %d], got %d", ACN_MAX_LEVELS, L);
-    ACN_REQUIRE(log2T >= 1 && log2T <= 30, "acn_hashgrid_fwd: log2_hashmap_size must be in [1, 30], got %d", log2T);
-    ACN_REQUIRE(F >= 1 && F <= 64, "acn_hashgrid_fwd: features_per_level must be in [1, 64], got %d", F);
-    ACN_REQUIRE(interp >= 0 && interp <= 2, "acn_hashgrid_fwd: bad interpolation %d", interp);
-    ACN_REQUIRE(res != nullptr, "acn_hashgrid_fwd: res is NULL");
+    Res32 r;
+    if (const int rc = check_grid("acn_hashgrid_fwd", M, L, log2T, F, 64, interp, res, r)) return rc;
     if (M == 0) return ACN_OK;
     ACN_REQUIRE(x01 && table && out, "acn_hashgrid_fwd: NULL pointer");
-    Res32 r{};
-    for (int i = 0; i < L; ++i) r.v[i] = res[i];
-    const int64_t threads = M * L;
-    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+    const dim3 grid = blocks(M * L), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (F == 2) {
-        const bool buf = ACN_HASH_FWD_BUF && interp != 0 && ((uint64_t)L << (log2T + 3)) <= (1ull << 31);
-        if (buf && interp == 1) hipLaunchKernelGGL(hashgrid_fwd_f2_buf<1>, grid, block, 0, s, x01, M, (const float2*)table, r, L, log2T, (float2*)out);
-        else if (buf) hipLaunchKernelGGL(hashgrid_fwd_f2_buf<2>, grid, block, 0, s, x01, M, (const float2*)table, r, L, log2T, (float2*)out);
-        else if (interp == 0) hipLaunchKernelGGL(hashgrid_fwd_f2<0>, grid, block, 0, s, x01, M, (const float2*)table, r, L, log2T, (float2*)out);
-        else if (interp == 1) hipLaunchKernelGGL(hashgrid_fwd_f2<1>, grid, block, 0, s, x01, M, (const float2*)table, r, L, log2T, (float2*)out);
-        else hipLaunchKernelGGL(hashgrid_fwd_f2<2>, grid, block, 0, s, x01, M, (const float2*)table, r, L, log2T, (float2*)out);
-    } else {
-        if (interp == 0) hipLaunchKernelGGL(hashgrid_fwd_gen<0>, grid, block, 0, s, x01, M, table, r, L, log2T, F, out);
-        else if (interp == 1) hipLaunchKernelGGL(hashgrid_fwd_gen<1>, grid, block, 0, s, x01, M, table, r, L, log2T, F, out);
-        else hipLaunchKernelGGL(hashgrid_fwd_gen<2>, grid, block, 0, s, x01, M, table, r, L, log2T, F, out);
-    }
+    with_interp(interp, [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        const float2* t2 = (const float2*)table;
+        float2* o2 = (float2*)out;
+        if (F != 2) {
+            hipLaunchKernelGGL(hashgrid_fwd_gen<I>, grid, block, 0, s, x01, M, table, r, L, log2T, F, out);
+            return;
+        }
+        if constexpr (I != 0) {
+            if (table_fits_buffer(L, log2T)) {
+                hipLaunchKernelGGL(hashgrid_fwd_f2_buf<I>, grid, block, 0, s, x01, M, t2, r, L, log2T, o2);
+                return;
+            }
+        }
+        hipLaunchKernelGGL(hashgrid_fwd_f2<I>, grid, block, 0, s, x01, M, t2, r, L, log2T, o2);
+    });
     return acn_check_launch("acn_hashgrid_fwd");
 }
 
 extern "C" int acn_hashgrid_bwd(const float* x01, int64_t M, const float* grad_out, const int32_t* res, int L,
                                 int log2T, int F, int interp, float* grad_table, void* stream) {
-    ACN_REQUIRE(M >= 0, "acn_hashgrid_bwd: M must be >= 0");
-    ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS, "acn_hashgrid_bwd: levels must be in [1, %d], got %d", ACN_MAX_LEVELS, L);
-    ACN_REQUIRE(log2T >= 1 && log2T <= 30, "acn_hashgrid_bwd: log2_hashmap_size must be in [1, 30], got %d", log2T);
-    ACN_REQUIRE(F >= 1 && F <= 64, "acn_hashgrid_bwd: features_per_level must be in [1, 64], got %d", F);
-    ACN_REQUIRE(interp >= 0 && interp <= 2, "acn_hashgrid_bwd: bad interpolation %d", interp);
-    ACN_REQUIRE(res != nullptr, "acn_hashgrid_bwd: res is NULL");
+    Res32 r;
+    if (const int rc = check_grid("acn_hashgrid_bwd", M, L, log2T, F, 64, interp, res, r)) return rc;
     if (M == 0) return ACN_OK;
     ACN_REQUIRE(x01 && grad_out && grad_table, "acn_hashgrid_bwd: NULL pointer");
-    Res32 r{};
-    for (int i = 0; i < L; ++i) r.v[i] = res[i];
+    const dim3 block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (F == 2 && interp != 0 && ACN_HASH_BWD_PPL > 0) {
-        constexpr int PPL = ACN_HASH_BWD_PPL > 0 ? ACN_HASH_BWD_PPL : 1;
-        const MergeCfg mc = merge_cfg(L, log2T, ACN_HASH_BWD_MERGE_SA);
-        if (mc.LM > 0) {
-            GradTables t{};
-            t.t[0] = grad_table;
-            int64_t items = 0;
-            for (int l = 0; l < mc.LM; ++l) items += (M + (1ll << mc.clog2[l]) - 1) >> mc.clog2[l];
-            const dim3 mgrid((unsigned)(items < 1024 ? items : 1024)), block(256);
-            if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_merge<1>, mgrid, block, 0, s, x01, nullptr, nullptr, nullptr, 1, M, grad_out, t, r, L, log2T, mc);
-            else hipLaunchKernelGGL(hashgrid_bwd_merge<2>, mgrid, block, 0, s, x01, nullptr, nullptr, nullptr, 1, M, grad_out, t, r, L, log2T, mc);
-        }
-        if (mc.LM < L) {
-            const int64_t waves = ((M + 4 * PPL - 1) / (4 * PPL)) * (L - mc.LM);
-            const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-            if (interp == 1) hipLaunchKernelGGL((hashgrid_bwd_rle<1, PPL>), grid, block, 0, s, x01, M, grad_out, r, L, log2T, grad_table, mc.LM);
-            else hipLaunchKernelGGL((hashgrid_bwd_rle<2, PPL>), grid, block, 0, s, x01, M, grad_out, r, L, log2T, grad_table, mc.LM);
-        }
-        return acn_check_launch("acn_hashgrid_bwd");
+    if (F == 2 && interp != 0) {  // the coarse levels merged per workgroup, the others on the run merge
+        const MergeCfg mc = merge_cfg(L, log2T, kMergeLevels);
+        with_lerp(interp, [&](auto i) {
+            constexpr int I = decltype(i)::value;
+            if (mc.LM > 0) {
+                int64_t items = 0;
+                for (int l = 0; l < mc.LM; ++l) items += (M + (1ll << mc.clog2[l]) - 1) >> mc.clog2[l];
+                const dim3 mgrid((unsigned)(items < 1024 ? items : 1024));
+                hipLaunchKernelGGL(hashgrid_bwd_merge<I>, mgrid, block, 0, s, x01, M, grad_out, grad_table, r, L, log2T, mc);
+            }
+            if (mc.LM < L) {
+                const int64_t waves = ((M + 4 * kRunPoints - 1) / (4 * kRunPoints)) * (L - mc.LM);
+                hipLaunchKernelGGL(hashgrid_bwd_rle<I>, blocks(waves * 64), block, 0, s, x01, M, grad_out, r, L, log2T, grad_table, mc.LM);
+            }
+        });
+    } else {
+        with_interp(interp, [&](auto i) {
+            hipLaunchKernelGGL(hashgrid_bwd_gen<decltype(i)::value>, blocks(M * L), block, 0, s, x01, M, grad_out, r, L, log2T, F, grad_table);
+        });
     }
-    if (F == 2 && interp != 0) {
-        const int64_t waves = ((M + 3) / 4) * L;
-        const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_f2<1>, grid, block, 0, s, x01, M, grad_out, r, L, log2T, grad_table);
-        else hipLaunchKernelGGL(hashgrid_bwd_f2<2>, grid, block, 0, s, x01, M, grad_out, r, L, log2T, grad_table);
-        return acn_check_launch("acn_hashgrid_bwd");
-    }
-    const int64_t threads = M * L;
-    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-    if (interp == 0) hipLaunchKernelGGL(hashgrid_bwd_gen<0>, grid, block, 0, s, x01, M, grad_out, r, L, log2T, F, grad_table);
-    else if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_gen<1>, grid, block, 0, s, x01, M, grad_out, r, L, log2T, F, grad_table);
-    else hipLaunchKernelGGL(hashgrid_bwd_gen<2>, grid, block, 0, s, x01, M, grad_out, r, L, log2T, F, grad_table);
     return acn_check_launch("acn_hashgrid_bwd");
 }
 
@@ -1051,100 +1028,74 @@ extern "C" int acn_sh_fwd(const float* d, int64_t M, int levels, float* out, voi
 extern "C" int acn_hashgrid_bwd_input(const float* x01, int64_t M, const float* grad_out, const float* table,
                                       const int32_t* res, int L, int log2T, int F, int interp, float* grad_x,
                                       void* stream) {
-    ACN_REQUIRE(M >= 0, "acn_hashgrid_bwd_input: M must be >= 0");
-    ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS, "acn_hashgrid_bwd_input: levels must be in [1, %d], got %d", ACN_MAX_LEVELS, L);
-    ACN_REQUIRE(log2T >= 1 && log2T <= 30, "acn_hashgrid_bwd_input: log2_hashmap_size must be in [1, 30], got %d", log2T);
-    ACN_REQUIRE(F >= 1, "acn_hashgrid_bwd_input: features_per_level must be >= 1, got %d", F);
-    ACN_REQUIRE(interp >= 0 && interp <= 2, "acn_hashgrid_bwd_input: bad interpolation %d", interp);
-    ACN_REQUIRE(res != nullptr, "acn_hashgrid_bwd_input: res is NULL");
+    Res32 r;
+    if (const int rc = check_grid("acn_hashgrid_bwd_input", M, L, log2T, F, 0, interp, res, r)) return rc;
     if (M == 0) return ACN_OK;
     ACN_REQUIRE(x01 && grad_out && table && grad_x, "acn_hashgrid_bwd_input: NULL pointer");
-    Res32 r{};
-    for (int i = 0; i < L; ++i) r.v[i] = res[i];
     const dim3 block(256);
     hipStream_t s = (hipStream_t)stream;
-    auto blocks = [](int64_t threads) { return dim3((unsigned)((threads + 255) / 256)); };
     if (interp == 0) {  // rint() is piecewise constant: the gradient is exactly 0
         hipLaunchKernelGGL(zero_f32, blocks(3 * M), block, 0, s, grad_x, 3 * M);
-    } else if (F == 2 && ((uint64_t)L << (log2T + 3)) <= (1ull << 31)) {
-        const float2* g = (const float2*)grad_out;
-        const float2* t = (const float2*)table;
-        if ((L & (L - 1)) == 0) {
-            if (interp == 1) hipLaunchKernelGGL((hashgrid_bwd_input_f2<1, true>), blocks(M * L), block, 0, s, x01, M, g, t, r, L, log2T, grad_x);
-            else hipLaunchKernelGGL((hashgrid_bwd_input_f2<2, true>), blocks(M * L), block, 0, s, x01, M, g, t, r, L, log2T, grad_x);
+    } else with_lerp(interp, [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        if (F == 2 && table_fits_buffer(L, log2T)) {
+            with_bool((L & (L - 1)) == 0, [&](auto tree) {
+                constexpr bool TREE = decltype(tree)::value;
+                hipLaunchKernelGGL((hashgrid_bwd_input_f2<I, TREE>), blocks(TREE ? M * L : M), block, 0, s, x01, M,
+                                   (const float2*)grad_out, (const float2*)table, r, L, log2T, grad_x);
+            });
         } else {
-            if (interp == 1) hipLaunchKernelGGL((hashgrid_bwd_input_f2<1, false>), blocks(M), block, 0, s, x01, M, g, t, r, L, log2T, grad_x);
-            else hipLaunchKernelGGL((hashgrid_bwd_input_f2<2, false>), blocks(M), block, 0, s, x01, M, g, t, r, L, log2T, grad_x);
+            hipLaunchKernelGGL(hashgrid_bwd_input_gen<I>, blocks(M), block, 0, s, x01, M, grad_out, table, r, L, log2T, F, grad_x);
         }
-    } else {
-        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_input_gen<1>, blocks(M), block, 0, s, x01, M, grad_out, table, r, L, log2T, F, grad_x);
-        else hipLaunchKernelGGL(hashgrid_bwd_input_gen<2>, blocks(M), block, 0, s, x01, M, grad_out, table, r, L, log2T, F, grad_x);
-    }
+    });
     return acn_check_launch("acn_hashgrid_bwd_input");
 }
 
 extern "C" int acn_hashgrid_bwd_input_bwd(const float* x01, int64_t M, const float* grad_out, const float* gg_x,
                                           const float* table, const int32_t* res, int L, int log2T, int F, int interp,
                                           float* gg_out, float* g_x, void* stream) {
-    ACN_REQUIRE(M >= 0, "acn_hashgrid_bwd_input_bwd: M must be >= 0");
-    ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS, "acn_hashgrid_bwd_input_bwd: levels must be in [1, %d], got %d", ACN_MAX_LEVELS, L);
-    ACN_REQUIRE(log2T >= 1 && log2T <= 30, "acn_hashgrid_bwd_input_bwd: log2_hashmap_size must be in [1, 30], got %d", log2T);
-    ACN_REQUIRE(F >= 1, "acn_hashgrid_bwd_input_bwd: features_per_level must be >= 1, got %d", F);
-    ACN_REQUIRE(interp >= 0 && interp <= 2, "acn_hashgrid_bwd_input_bwd: bad interpolation %d", interp);
-    ACN_REQUIRE(res != nullptr, "acn_hashgrid_bwd_input_bwd: res is NULL");
+    Res32 r;
+    if (const int rc = check_grid("acn_hashgrid_bwd_input_bwd", M, L, log2T, F, 0, interp, res, r)) return rc;
     if (M == 0 || (!gg_out && !g_x)) return ACN_OK;
     ACN_REQUIRE(x01 && grad_out && gg_x && table, "acn_hashgrid_bwd_input_bwd: NULL pointer");
-    Res32 r{};
-    for (int i = 0; i < L; ++i) r.v[i] = res[i];
     const dim3 block(256);
     hipStream_t s = (hipStream_t)stream;
-    auto blocks = [](int64_t threads) { return dim3((unsigned)((threads + 255) / 256)); };
     if (interp == 0) {  // the input gradient is identically 0: so are its derivatives
         if (gg_out) hipLaunchKernelGGL(zero_f32, blocks(M * L * F), block, 0, s, gg_out, M * L * F);
         if (g_x) hipLaunchKernelGGL(zero_f32, blocks(3 * M), block, 0, s, g_x, 3 * M);
-    } else if (F == 2 && ((uint64_t)L << (log2T + 3)) <= (1ull << 31)) {
-        const float2* g = (const float2*)grad_out;
-        const float2* t = (const float2*)table;
-        float2* gg = (float2*)gg_out;
-        if ((L & (L - 1)) == 0) {
-            if (interp == 1) hipLaunchKernelGGL((hashgrid_bwd_input_bwd_f2<1, true>), blocks(M * L), block, 0, s, x01, M, g, gg_x, t, r, L, log2T, gg, g_x);
-            else hipLaunchKernelGGL((hashgrid_bwd_input_bwd_f2<2, true>), blocks(M * L), block, 0, s, x01, M, g, gg_x, t, r, L, log2T, gg, g_x);
+    } else with_lerp(interp, [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        if (F == 2 && table_fits_buffer(L, log2T)) {
+            with_bool((L & (L - 1)) == 0, [&](auto tree) {
+                constexpr bool TREE = decltype(tree)::value;
+                hipLaunchKernelGGL((hashgrid_bwd_input_bwd_f2<I, TREE>), blocks(TREE ? M * L : M), block, 0, s, x01, M,
+                                   (const float2*)grad_out, gg_x, (const float2*)table, r, L, log2T, (float2*)gg_out, g_x);
+            });
         } else {
-            if (interp == 1) hipLaunchKernelGGL((hashgrid_bwd_input_bwd_f2<1, false>), blocks(M), block, 0, s, x01, M, g, gg_x, t, r, L, log2T, gg, g_x);
-            else hipLaunchKernelGGL((hashgrid_bwd_input_bwd_f2<2, false>), blocks(M), block, 0, s, x01, M, g, gg_x, t, r, L, log2T, gg, g_x);
+            hipLaunchKernelGGL(hashgrid_bwd_input_bwd_gen<I>, blocks(M), block, 0, s, x01, M, grad_out, gg_x, table, r, L, log2T, F, gg_out, g_x);
         }
-    } else {
-        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_input_bwd_gen<1>, blocks(M), block, 0, s, x01, M, grad_out, gg_x, table, r, L, log2T, F, gg_out, g_x);
-        else hipLaunchKernelGGL(hashgrid_bwd_input_bwd_gen<2>, blocks(M), block, 0, s, x01, M, grad_out, gg_x, table, r, L, log2T, F, gg_out, g_x);
-    }
+    });
     return acn_check_launch("acn_hashgrid_bwd_input_bwd");
 }
 
 extern "C" int acn_hashgrid_bwd_input_bwd_table(const float* x01, int64_t M, const float* grad_out, const float* gg_x,
                                                 const int32_t* res, int L, int log2T, int F, int interp,
                                                 float* grad_table, void* stream) {
-    ACN_REQUIRE(M >= 0, "acn_hashgrid_bwd_input_bwd_table: M must be >= 0");
-    ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS, "acn_hashgrid_bwd_input_bwd_table: levels must be in [1, %d], got %d", ACN_MAX_LEVELS, L);
-    ACN_REQUIRE(log2T >= 1 && log2T <= 30, "acn_hashgrid_bwd_input_bwd_table: log2_hashmap_size must be in [1, 30], got %d", log2T);
-    ACN_REQUIRE(F >= 1, "acn_hashgrid_bwd_input_bwd_table: features_per_level must be >= 1, got %d", F);
-    ACN_REQUIRE(interp >= 0 && interp <= 2, "acn_hashgrid_bwd_input_bwd_table: bad interpolation %d", interp);
-    ACN_REQUIRE(res != nullptr, "acn_hashgrid_bwd_input_bwd_table: res is NULL");
+    Res32 r;
+    if (const int rc = check_grid("acn_hashgrid_bwd_input_bwd_table", M, L, log2T, F, 0, interp, res, r)) return rc;
     if (M == 0 || interp == 0) return ACN_OK;   // Nearest: nothing depends on the table through grad_x
     ACN_REQUIRE(x01 && grad_out && gg_x && grad_table, "acn_hashgrid_bwd_input_bwd_table: NULL pointer");
-    Res32 r{};
-    for (int i = 0; i < L; ++i) r.v[i] = res[i];
     const dim3 block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (F == 2) {
-        const int64_t waves = ((M + 3) / 4) * L;
-        const dim3 grid((unsigned)((waves + 3) / 4));
-        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_f2<1>, grid, block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, grad_table);
-        else hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_f2<2>, grid, block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, grad_table);
-    } else {
-        const dim3 grid((unsigned)((M * L + 255) / 256));
-        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_gen<1>, grid, block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, F, grad_table);
-        else hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_gen<2>, grid, block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, F, grad_table);
-    }
+    with_lerp(interp, [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        if (F == 2) {
+            const int64_t waves = ((M + 3) / 4) * L;
+            hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_f2<I>, blocks(waves * 64), block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, grad_table);
+        } else {
+            hipLaunchKernelGGL(hashgrid_bwd_input_bwd_table_gen<I>, blocks(M * L), block, 0, s, x01, M, grad_out, gg_x, r, L, log2T, F, grad_table);
+        }
+    });
     return acn_check_launch("acn_hashgrid_bwd_input_bwd_table");
 }
 
@@ -1172,19 +1123,21 @@ extern "C" int acn_hashgrid_fwd_pairs(const float* x01, const int32_t* pk, const
                 "acn_hashgrid_fwd_pairs: bad arguments");
     ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS && log2T >= 1 && log2T <= 30 && interp >= 0 && interp <= 2,
                 "acn_hashgrid_fwd_pairs: bad grid configuration");
-    Res32 r{};
-    for (int i = 0; i < L; ++i) r.v[i] = res[i];
+    const Res32 r = pack_res(res, L);
     Tables t{};
     for (int k = 0; k < K; ++k) t.t[k] = (const float2*)tables[k];
     const dim3 grid(2048), block(256);  // grid-stride to the device slot count
     hipStream_t s = (hipStream_t)stream;
-    if (interp == 0) hipLaunchKernelGGL(hashgrid_fwd_pairs<0>, grid, block, 0, s, x01, pk, seg, K, t, r, L, log2T, (float2*)out);
-    else if (ACN_HASH_FWD_BUF && ((uint64_t)L << (log2T + 3)) <= (1ull << 31)) {
-        if (interp == 1) hipLaunchKernelGGL((hashgrid_fwd_pairs<1, true>), grid, block, 0, s, x01, pk, seg, K, t, r, L, log2T, (float2*)out);
-        else hipLaunchKernelGGL((hashgrid_fwd_pairs<2, true>), grid, block, 0, s, x01, pk, seg, K, t, r, L, log2T, (float2*)out);
-    }
-    else if (interp == 1) hipLaunchKernelGGL(hashgrid_fwd_pairs<1>, grid, block, 0, s, x01, pk, seg, K, t, r, L, log2T, (float2*)out);
-    else hipLaunchKernelGGL(hashgrid_fwd_pairs<2>, grid, block, 0, s, x01, pk, seg, K, t, r, L, log2T, (float2*)out);
+    with_interp(interp, [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        if constexpr (I != 0) {
+            if (table_fits_buffer(L, log2T)) {
+                hipLaunchKernelGGL((hashgrid_fwd_pairs<I, true>), grid, block, 0, s, x01, pk, seg, K, t, r, L, log2T, (float2*)out);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((hashgrid_fwd_pairs<I, false>), grid, block, 0, s, x01, pk, seg, K, t, r, L, log2T, (float2*)out);
+    });
     return acn_check_launch("acn_hashgrid_fwd_pairs");
 }
 
@@ -1212,29 +1165,19 @@ extern "C" int acn_hashgrid_bwd_pairs_segmap(const float* x01, const int32_t* pk
                 "acn_hashgrid_bwd_pairs: bad arguments");
     ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS && log2T >= 1 && log2T <= 30 && (interp == 1 || interp == 2),
                 "acn_hashgrid_bwd_pairs: Linear / Smoothstep interpolation only");
-    Res32 r{};
-    for (int i = 0; i < L; ++i) r.v[i] = res[i];
+    const Res32 r = pack_res(res, L);
     GradTables t{};
     for (int k = 0; k < K; ++k) t.t[k] = grad_tables[k];
     SegMaps sm{};
     if (seg_now)
         for (int k = 0; k < K; ++k) sm.t[k] = seg_now[k];
-    const dim3 grid(2048), block(256);
     hipStream_t s = (hipStream_t)stream;
-    const MergeCfg mc = merge_cfg(L, log2T);
-    ACN_REQUIRE(!(table_sumsq && mc.LM > 0), "acn_hashgrid_bwd_pairs_sumsq: not available with the merged coarse "
-                "levels (ACN_HASH_BWD_MERGE)");
-    ACN_REQUIRE(!(seg_now && mc.LM > 0), "acn_hashgrid_bwd_pairs_segmap: not available with the merged coarse levels");
-    if (mc.LM > 0) {  // fixed grid (graph-replayable): items are counted from the device slot count
-        if (interp == 1) hipLaunchKernelGGL(hashgrid_bwd_merge<1>, dim3(512), block, 0, s, x01, pk, pidx, seg, K, (int64_t)0, grad_out, t, r, L, log2T, mc);
-        else hipLaunchKernelGGL(hashgrid_bwd_merge<2>, dim3(512), block, 0, s, x01, pk, pidx, seg, K, (int64_t)0, grad_out, t, r, L, log2T, mc);
-    }
-    if (mc.LM < L) {
-#define ACN_BWD_PAIRS(I, T) hipLaunchKernelGGL((hashgrid_bwd_pairs<I, 16, T>), grid, block, 0, s, x01, pk, pidx, seg, K, grad_out, t, r, L, log2T, mc.LM, table_sumsq, sm)
-        if (table_sumsq) { if (interp == 1) ACN_BWD_PAIRS(1, true); else ACN_BWD_PAIRS(2, true); }
-        else { if (interp == 1) ACN_BWD_PAIRS(1, false); else ACN_BWD_PAIRS(2, false); }
-#undef ACN_BWD_PAIRS
-    }
+    with_lerp(interp, [&](auto i) {
+        with_bool(table_sumsq != nullptr, [&](auto tele) {  // fixed grid (graph-replayable), strided to the slot count
+            hipLaunchKernelGGL((hashgrid_bwd_pairs<decltype(i)::value, decltype(tele)::value>), dim3(2048), dim3(256), 0, s,
+                               x01, pk, pidx, seg, K, grad_out, t, r, L, log2T, table_sumsq, sm);
+        });
+    });
     return acn_check_launch("acn_hashgrid_bwd_pairs");
 }
 
@@ -1245,25 +1188,13 @@ extern "C" int acn_hashgrid_pairs_mark(const float* x01, const int32_t* pk, cons
                 "acn_hashgrid_pairs_mark: bad arguments");
     ACN_REQUIRE(L >= 1 && L <= ACN_MAX_LEVELS && log2T >= 1 && log2T <= 30 && (interp == 1 || interp == 2),
                 "acn_hashgrid_pairs_mark: Linear / Smoothstep interpolation only");
-    Res32 r{};
-    for (int i = 0; i < L; ++i) r.v[i] = res[i];
-    GradTables t{};
+    const Res32 r = pack_res(res, L);
     SegMaps sm{};
-    // The kernel tells runs apart by their target address.  There are no gradient tables here, so expert k gets the
-    // address range a table of its own would have, k + 1 table sizes from 0: disjoint ranges, never null, and
-    // nothing is written through them.  (Derived from the maps' own addresses, rows of two experts whose maps lie
-    // closer than a table's size could share an address, and the second expert's segment went unmarked.)
-    const uint64_t table_bytes = ((uint64_t)L << log2T) * 2 * sizeof(float);
-    for (int k = 0; k < K; ++k) {
-        sm.t[k] = seg_now[k];
-        t.t[k] = reinterpret_cast<float*>((uintptr_t)((uint64_t)(k + 1) * table_bytes));
-    }
+    for (int k = 0; k < K; ++k) sm.t[k] = seg_now[k];
     hipStream_t s = (hipStream_t)stream;
-    if (interp == 1)
-        hipLaunchKernelGGL((hashgrid_bwd_pairs<1, 16, false, true>), dim3(2048), dim3(256), 0, s, x01, pk, pidx, seg, K,
-                           (const float*)nullptr, t, r, L, log2T, 0, (double*)nullptr, sm);
-    else
-        hipLaunchKernelGGL((hashgrid_bwd_pairs<2, 16, false, true>), dim3(2048), dim3(256), 0, s, x01, pk, pidx, seg, K,
-                           (const float*)nullptr, t, r, L, log2T, 0, (double*)nullptr, sm);
+    with_lerp(interp, [&](auto i) {
+        hipLaunchKernelGGL((hashgrid_bwd_pairs<decltype(i)::value, false, true>), dim3(2048), dim3(256), 0, s, x01, pk,
+                           pidx, seg, K, (const float*)nullptr, GradTables{}, r, L, log2T, (double*)nullptr, sm);
+    });
     return acn_check_launch("acn_hashgrid_pairs_mark");
 }

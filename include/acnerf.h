@@ -908,8 +908,7 @@ int acn_hashgrid_bwd_pairs(const float* x01, const int32_t* pk, const int32_t* p
 /* acn_hashgrid_bwd_pairs that also adds, to the device double *table_sumsq, the change of the squared
  * norm of the gradient tables (returning atomics: sum of new^2 - old^2, which telescopes per row), i.e.
  * the tables' share of clip_grad_norm_'s sum of squares (runtime_adapt.py:305-307) when the tables start
- * the step at zero -- no pass over the K x 128 MiB gradients.  Not combinable with the merged coarse
- * levels (ACN_HASH_BWD_MERGE builds: returns an error). */
+ * the step at zero -- no pass over the K x 128 MiB gradients. */
 int acn_hashgrid_bwd_pairs_sumsq(const float* x01, const int32_t* pk, const int32_t* pidx, const int64_t* seg,
                                  int K, const float* grad_out, float* const* grad_tables, const int32_t* res, int L,
                                  int log2T, int interp, double* table_sumsq, void* stream);

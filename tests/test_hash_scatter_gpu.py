@@ -7,7 +7,7 @@ lost, doubled or misplaced contribution of any size fails.  Generic float inputs
 bound tol_row = (16 + n_row) * 2^-24 * A_row, with exact zeros where nothing contributes.  test_hash_scatter_cpu
 shows that mutations of an fp32 scatter fail both checks.
 
-Reached here (default build: ACN_HASH_BWD_PPL = 16, ACN_HASH_BWD_MERGE_SA = 6, ACN_HASH_BWD_MERGE = 0):
+Reached here (16 points per lane stretch; the standalone scatter merges 6 levels, the pair list none):
   acn_hashgrid_bwd, F = 2, Linear / Smoothstep: hashgrid_bwd_merge (levels 0..5: chunk edges 2^8..2^12, the item
       loop past 1024 items, the crowded-LDS fallback, zero sums at the flush, 64-B segments spanning levels at
       log2T < 3) and hashgrid_bwd_rle (levels >= 6: runs across the 16-point stretch and the 64-point wave);
