@@ -27,5 +27,6 @@ from .trunc_exp import trunc_exp  # noqa: E402,F401
 from .data import (DeviceRaysDataset, ImageMetadata, Task, TaskDataset, get_dataset,  # noqa: E402,F401
                    get_image_metadata)
 from . import clusters  # noqa: E402,F401
+from .appearance import AppearanceAffine  # noqa: E402,F401
 from . import metrics  # noqa: E402,F401
 from .metrics import depth_metrics, evaluate_image, image_metrics, ssim, ssim_image  # noqa: E402,F401

@@ -175,6 +175,10 @@ SIGNATURES = {
     "acn_distortion_dense": ([vp, vp, i64, i32, vp, vp, vp, vp], C.c_int),
     "acn_depth_loss_packed": ([vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp], C.c_int),
     "acn_depth_loss_dense": ([vp, vp, i64, i32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp], C.c_int),
+    # appearance.hip
+    "acn_appearance_mse_workspace_bytes": ([i32], C.c_size_t),
+    "acn_appearance_mse": ([vp, vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
+    "acn_appearance_apply": ([vp, vp, i64, vp, vp, i32, vp, vp], C.c_int),
     # resample.hip
     "acn_resample_pdf": ([vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp], C.c_int),
     # interlevel.hip

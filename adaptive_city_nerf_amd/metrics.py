@@ -179,7 +179,9 @@ def depth_metrics(pred: Tensor, gt: Tensor) -> Dict[str, float]:
 def evaluate_image(model, *, H: int, W: int, fx: float, fy: float, cx: float, cy: float, c2w: Tensor, scene_box,
                    gt_srgb: Tensor, metrics_space: str = "linear", **render_kwargs):
     """``render_image`` followed by ``image_metrics``: (rgb (H, W, 3), depth, acc, {"psnr", "ssim"}) of one validation
-    view (the per-image body of the reference's runtime_evaluate, without LPIPS)."""
+    view (the per-image body of the reference's runtime_evaluate, without LPIPS).  ``appearance=`` and
+    ``image_index=`` among the render arguments correct the frame with that image's affine colour transform
+    (render_image) before the metrics are taken."""
     from .ray_rendering import render_image
     rgb, depth, acc = render_image(model, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, c2w=c2w, scene_box=scene_box,
                                    **render_kwargs)

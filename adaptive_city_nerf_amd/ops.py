@@ -535,6 +535,73 @@ def mse_linear_bwd(pred: torch.Tensor, gt: torch.Tensor, g_loss: torch.Tensor) -
     return out.view(pred.shape)
 
 
+_APPEARANCE_WS = {}
+
+
+def _appearance_ws(device, I: int) -> torch.Tensor:
+    """Zeroed workspace of acn_appearance_mse per (device, stream), handled like _mse_ws: the ticket counter returns
+    to 0 after every call, and under stream capture every captured call gets a workspace of its own."""
+    nbytes = int(_lib.lib().acn_appearance_mse_workspace_bytes(int(I)))
+    if torch.cuda.is_current_stream_capturing():
+        return _lib.capture_keepalive(torch.zeros(nbytes, dtype=torch.uint8, device=device))
+    key = (device, int(torch.cuda.current_stream(device).cuda_stream))
+    ws = _APPEARANCE_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _APPEARANCE_WS[key] = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _appearance_args(rgb, slots, A, b, what: str):
+    """The (N, 3) colours, (N,) int32 slots, (I, 3, 3) matrices and (I, 3) offsets as contiguous device tensors."""
+    require_hip(rgb, what)
+    p = _f32(rgb).reshape(-1, 3)
+    N = p.shape[0]
+    s = slots.detach().reshape(-1)
+    if s.dtype != torch.int32:
+        s = s.to(torch.int32)
+    s = s.contiguous()
+    Av, bv = _f32(A), _f32(b)
+    if Av.dim() != 3 or Av.shape[1:] != (3, 3) or Av.shape[0] < 1 or bv.shape != (Av.shape[0], 3):
+        raise AcnError(f"{what}: A must be (I >= 1, 3, 3) and b (I, 3), got {tuple(A.shape)} and {tuple(b.shape)}")
+    if s.numel() != N or any(t.device != p.device for t in (s, Av, bv)):
+        raise AcnError(f"{what}: slots must be ({N},) and slots, A, b on the colours' device, got "
+                       f"{tuple(slots.shape)} on {slots.device}, A on {A.device}, b on {b.device}")
+    return p, s, Av, bv, N, int(Av.shape[0])
+
+
+def appearance_mse(pred: torch.Tensor, gt: torch.Tensor, slots: torch.Tensor, A: torch.Tensor, b: torch.Tensor,
+                   want_grad: bool = True):
+    """(loss, g_pred, g_A, g_b) of the linear-colour MSE on the per-image corrected prediction
+    c = A[slot] pred + b[slot] (acn_appearance_mse): loss = mean((clamp01(c) - gt_linear(gt))^2) as a
+    0-d tensor and, at g_loss = 1, its gradients to ``pred`` (N, 3), ``A`` (I, 3, 3) and ``b`` (I, 3), from one
+    launch.  A slot outside [0, I) is the identity and reaches no parameter; a slot no ray has gets exact zeros.
+    Sums in float64, one fp32 rounding per output, bitwise reproducible, no host synchronisation.  With
+    ``want_grad=False`` the gradients are None and the loss has the same bits."""
+    p, s, Av, bv, N, I = _appearance_args(pred, slots, A, b, "appearance_mse")
+    g = _f32(gt).reshape(-1, 3)
+    if N == 0 or g.shape[0] != N or g.device != p.device:
+        raise AcnError(f"appearance_mse: pred / gt must both be (N >= 1, 3) on one device, got {tuple(pred.shape)} "
+                       f"and {tuple(gt.shape)}")
+    loss = torch.empty((), device=p.device, dtype=torch.float32)
+    g_pred = g_A = g_b = None
+    if want_grad:
+        g_pred, g_A, g_b = torch.empty_like(p), torch.empty_like(Av), torch.empty_like(bv)
+    ws = _appearance_ws(p.device, I)
+    check(_lib.lib().acn_appearance_mse(ptr(p), ptr(g), ptr(s), N, ptr(Av), ptr(bv), I, ptr(loss), ptr(g_pred),
+                                        ptr(g_A), ptr(g_b), ptr(ws), ws.numel(), stream_of(p)), "acn_appearance_mse")
+    return loss, (None if g_pred is None else g_pred.view(pred.shape)), g_A, g_b
+
+
+def appearance_apply(rgb: torch.Tensor, slots: torch.Tensor, A: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """c = A[slot] rgb + b[slot] per pixel (acn_appearance_apply), evaluated in float64 and rounded once, not clamped;
+    a slot outside [0, I) returns the input bits.  ``rgb`` is (..., 3) with one slot per pixel."""
+    p, s, Av, bv, N, I = _appearance_args(rgb, slots, A, b, "appearance_apply")
+    out = torch.empty_like(p)
+    check(_lib.lib().acn_appearance_apply(ptr(p), ptr(s), N, ptr(Av), ptr(bv), I, ptr(out), stream_of(p)),
+          "acn_appearance_apply")
+    return out.view(rgb.shape)
+
+
 def get_rays_image(H: int, W: int, fx: float, fy: float, cx: float, cy: float, c2w: torch.Tensor,
                    aabb: Optional[torch.Tensor], device, center_pixels: bool = True, near: Optional[float] = None,
                    far: Optional[float] = None, near_far_override=None, apply_clamp: bool = True):

@@ -1247,9 +1247,12 @@ def render_normal_image(model, *, H: int, W: int, fx: float, fy: float, cx: floa
 def render_image(model, *, H: int, W: int, fx: float, fy: float, cx: float, cy: float, c2w: Tensor, scene_box,
                  params=None, active_module: Optional[int] = None, ray_samples: int = 64, chunk_points: int = 1 << 16,
                  bg_color_default: str = "white", center_pixels: bool = True, use_amp: bool = False,
-                 **kwargs) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+                 appearance=None, image_index=None, **kwargs) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
     """Full frame: per-pixel rays (one fused HIP kernel), render_rays, (H,W,3) clamp (:577-627).
-    ``use_amp`` is accepted for interface compatibility; the HIP path computes in fp32."""
+    ``use_amp`` is accepted for interface compatibility; the HIP path computes in fp32.
+    ``appearance`` (an appearance.AppearanceAffine) with ``image_index`` corrects the clamped frame
+    with that image's matrix and offset (one more launch; the result is not clamped again); an index the model has no
+    slot for leaves the frame bit-identical."""
     device = next(model.parameters()).device
     rays, _ = ops.get_rays_image(H, W, fx, fy, cx, cy, c2w, scene_box.aabb, device, center_pixels=center_pixels,
                                  near_far_override=(None, None), apply_clamp=True)
@@ -1257,4 +1260,8 @@ def render_image(model, *, H: int, W: int, fx: float, fy: float, cx: float, cy: 
                                          active_module=active_module, bg_color_default=bg_color_default,
                                          chunk=chunk_points, _want_weights=False, **kwargs)
     rgb_lin = rgb_lin.view(H, W, 3).float().clamp_(0, 1)
+    if appearance is not None:
+        if image_index is None:
+            raise ValueError("render_image: an appearance model needs image_index (the frame's image index)")
+        rgb_lin = appearance(rgb_lin, image_index)
     return rgb_lin, (None if depth is None else depth.view(-1)), (None if acc is None else acc.view(-1))

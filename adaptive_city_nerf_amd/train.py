@@ -57,6 +57,67 @@ def mse_color_loss(pred_rgb, gt_rgb, color_space: str, reduction: str = "mean"):
     return F.mse_loss(pred_rgb, gt_rgb, reduction=reduction)
 
 
+class _AppearanceMSEFn(torch.autograd.Function):
+    """mse_color_loss(appearance(pred, img), gt, 'linear') as one HIP launch (appearance.hip) that
+    returns the loss and keeps its gradients to the prediction, the matrices and the offsets for the backward, which
+    multiplies them by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, slots, A, b):
+        want = any(ctx.needs_input_grad)
+        loss, g_pred, g_A, g_b = ops.appearance_mse(pred, gt, slots, A, b, want_grad=want)
+        ctx.set_materialize_grads(False)
+        if want:
+            ctx.save_for_backward(g_pred, g_A, g_b)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 5
+        g_pred, g_A, g_b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return (g * g_pred if need[0] else None, None, None, g * g_A if need[3] else None,
+                g * g_b if need[4] else None)
+
+
+def appearance_mse_loss(pred_rgb, gt_rgb, img_indices, appearance, color_space: str, reduction: str = "mean"):
+    """mse_color_loss on the per-image corrected prediction ``appearance(pred_rgb, img_indices)``
+    (appearance.AppearanceAffine).  In colour space ``linear`` with reduction ``mean``, on fp32 device
+    tensors and outside second_order(), the correction, the loss and the gradients to the prediction and to the
+    appearance parameters are one HIP launch (ops.appearance_mse); otherwise it is the composed torch chain, which is
+    differentiable any number of times and works on CPU tensors."""
+    from .ray_rendering import _second_order
+    if (str(color_space).lower() == "linear" and reduction == "mean" and pred_rgb.is_cuda
+            and pred_rgb.dtype == torch.float32 and pred_rgb.numel() > 0 and pred_rgb.shape == gt_rgb.shape
+            and pred_rgb.shape[-1] == 3 and appearance.matrix.is_cuda and appearance.matrix.dtype == torch.float32
+            and not _second_order()):
+        slots = appearance.slots(img_indices)
+        if slots.numel() != pred_rgb.numel() // 3:
+            raise ValueError(f"appearance_mse_loss: {slots.numel()} image indices for {pred_rgb.numel() // 3} rays")
+        return _AppearanceMSEFn.apply(pred_rgb, gt_rgb.to(pred_rgb.device, torch.float32), slots, appearance.matrix,
+                                      appearance.offset)
+    from .appearance import _apply_torch
+    slots = appearance.slots(img_indices).to(pred_rgb.device)
+    corrected = _apply_torch(pred_rgb, slots, appearance.matrix.to(pred_rgb.device),
+                             appearance.offset.to(pred_rgb.device))
+    return mse_color_loss(corrected, gt_rgb, color_space, reduction)
+
+
+def _image_loss(pred_rgb, data, P, reduction, appearance, appearance_reg):
+    """The image term of compute_loss: mse_color_loss, or with an appearance model appearance_mse_loss on
+    ``data["img_indices"]`` plus ``appearance_reg`` times its regulariser."""
+    if appearance is None:
+        return mse_color_loss(pred_rgb, data["rgbs"], P.color_space, reduction)
+    if data.get("img_indices") is None:
+        raise ValueError("compute_loss: an appearance model needs data['img_indices'] (one image index per ray)")
+    loss = appearance_mse_loss(pred_rgb, data["rgbs"], data["img_indices"], appearance, P.color_space, reduction)
+    if appearance_reg:
+        loss = loss + float(appearance_reg) * appearance.regulariser()
+    return loss
+
+
 def compute_mse_loss(P, model, data, params=None, active_module=None, reduction: str = "mean", **render_kwargs):
     """losses.py:10-32: MSE between render_rays(...) rgb and data['rgbs'] in P.color_space."""
     gt_rgb = data["rgbs"]
@@ -68,7 +129,8 @@ def compute_mse_loss(P, model, data, params=None, active_module=None, reduction:
 
 def compute_loss(P, model, data, params=None, active_module=None, reduction: str = "mean",
                  distortion_weight: float = 0.0, proposal=None, interlevel_weight: float = 1.0,
-                 depth_weight: float = 0.0, sight_weight: float = 0.0, depth_eps=None, **render_kwargs):
+                 depth_weight: float = 0.0, sight_weight: float = 0.0, depth_eps=None, appearance=None,
+                 appearance_reg: float = 0.0, **render_kwargs):
     """compute_mse_loss plus ``distortion_weight`` times the mean distortion loss of the render's weights
     (ray_rendering.distortion_loss, every ray normalised to unit length): the mip-NeRF 360 regulariser against
     semi-transparent fog and floaters between the camera and the surface.  With weight 0 it is compute_mse_loss, from
@@ -84,6 +146,11 @@ def compute_loss(P, model, data, params=None, active_module=None, reduction: str
     multiple of the expected-depth term and of the line-of-sight term, against the targets ``data["depths"]`` (N,)
     (distance along the ray; NaN where a ray has none) with the half-width ``depth_eps`` (a float or (N,)), averaged
     over the rays that carry a target, on the weights of the pass the image loss is taken on.  With both 0 nothing
+    changes: the same calls, the same loss.
+
+    ``appearance`` (an appearance.AppearanceAffine) takes the image loss on the per-image corrected
+    colour (appearance_mse_loss, with the image index of every ray in ``data["img_indices"]``, the key TaskDataset
+    emits) and adds ``appearance_reg`` times its regulariser; the render itself is untouched.  With None nothing
     changes: the same calls, the same loss."""
     geo = {}
     if depth_weight or sight_weight:
@@ -96,22 +163,25 @@ def compute_loss(P, model, data, params=None, active_module=None, reduction: str
         pred_rgb, _, weights, _, (t_prop, w_prop), t_vals = render_rays(
             model, rays, ray_samples=P.ray_samples, params=params, active_module=active_module, chunk=P.chunk_points,
             proposal=proposal, return_proposal=True, return_t_vals=True, **render_kwargs)
-        loss = mse_color_loss(pred_rgb, data["rgbs"], P.color_space, reduction)
+        loss = _image_loss(pred_rgb, data, P, reduction, appearance, appearance_reg)
         if distortion_weight:
             loss = loss + float(distortion_weight) * distortion_loss(weights, t_vals, rays=rays, reduction="mean")
         if geo:
             loss = loss + depth_loss(weights, t_vals, data["depths"], depth_eps, rays=rays, reduction="mean", **geo)
         return loss + float(interlevel_weight) * interlevel_loss(t_vals, weights, t_prop, w_prop, rays=rays,
                                                                  reduction="mean")
-    if not distortion_weight and not geo:
+    if not distortion_weight and not geo and appearance is None:
         return compute_mse_loss(P, model, data, params=params, active_module=active_module, reduction=reduction,
                                 **render_kwargs)
-    gt_rgb = data["rgbs"]
     rays = data["rays"]
+    if not distortion_weight and not geo:
+        pred_rgb, *_ = render_rays(model, rays, ray_samples=P.ray_samples, params=params, active_module=active_module,
+                                   chunk=P.chunk_points, **render_kwargs)
+        return _image_loss(pred_rgb, data, P, reduction, appearance, appearance_reg)
     pred_rgb, _, weights, _, t_vals = render_rays(model, rays, ray_samples=P.ray_samples, params=params,
                                                   active_module=active_module, chunk=P.chunk_points,
                                                   return_t_vals=True, **render_kwargs)
-    loss = mse_color_loss(pred_rgb, gt_rgb, P.color_space, reduction)
+    loss = _image_loss(pred_rgb, data, P, reduction, appearance, appearance_reg)
     if distortion_weight:
         loss = loss + float(distortion_weight) * distortion_loss(weights, t_vals, rays=rays, reduction="mean")
     if geo:
@@ -132,7 +202,8 @@ def _depth_terms(depth_weight, sight_weight, depths, depth_eps, what: str) -> di
 def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Optional[float] = 1.0,
                group=None, shared: Optional[list] = None, grad_scaler=None, distortion_weight: float = 0.0,
                proposal=None, interlevel_weight: float = 1.0, depths=None, depth_weight: float = 0.0,
-               sight_weight: float = 0.0, depth_eps=None, **render_kwargs) -> torch.Tensor:
+               sight_weight: float = 0.0, depth_eps=None, img_indices=None, appearance=None,
+               appearance_reg: float = 0.0, **render_kwargs) -> torch.Tensor:
     """One optimizer update of runtime_adapt (runtime_adapt.py:288-313).  Returns the loss (device).
     ``distortion_weight`` > 0 adds that multiple of the mean distortion loss (compute_loss) to the MSE.
     ``n_importance`` = K > 0 (through ``render_kwargs``, with ``jitter_fine``) trains on the coarse-to-fine render
@@ -141,6 +212,11 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
     interlevel loss (compute_loss), which trains the proposal: its parameters must be in ``optimizer``.
     ``depth_weight`` / ``sight_weight`` > 0 add depth supervision against ``depths`` (N,) with the half-width
     ``depth_eps`` (compute_loss); with both 0, ``depths`` is not looked at.
+    ``appearance`` (an appearance.AppearanceAffine) trains on the per-image corrected colour (compute_loss) with the
+    image index of every ray in ``img_indices`` (N,), plus ``appearance_reg`` times its regulariser; some of its
+    parameters must be in ``optimizer``.  FusedAdam's folded clip norm is taken over every gradient-carrying tensor of
+    the optimizer, so it includes the appearance gradients; without FusedAdam they are clipped with the base's too.
+    With None, ``img_indices`` is not looked at.
 
     ``group`` (expert parallel): ``rays`` / ``rgbs`` are this rank's shard of the global batch, the
     container's experts are distributed over the group (expert_parallel.adapt_step_expert_parallel);
@@ -160,11 +236,21 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
                          "with a group)")
     if group is not None and proposal is not None:
         raise ValueError("adapt_step: the expert-parallel step renders one stratified pass (no proposal with a group)")
+    if group is not None and appearance is not None:
+        raise ValueError("adapt_step: the expert-parallel step has no appearance model (appearance must be None with "
+                         "a group)")
     if proposal is not None:
         held = {id(p) for g in optimizer.param_groups for p in g["params"]}
         if not any(id(p) in held for p in proposal.parameters()):
             raise ValueError("adapt_step: none of the proposal's parameters is in the optimizer; the interlevel loss "
                              "would train nothing")
+    if appearance is not None:
+        if img_indices is None:
+            raise ValueError("adapt_step: an appearance model needs img_indices (one image index per ray)")
+        held = {id(p) for g in optimizer.param_groups for p in g["params"]}
+        if not any(id(p) in held for p in appearance.parameters()):
+            raise ValueError("adapt_step: none of the appearance model's parameters is in the optimizer; the "
+                             "correction would train nothing")
     if group is not None and torch.distributed.is_initialized() and torch.distributed.get_world_size(group) > 1:
         from .expert_parallel import HipBackend, adapt_step_expert_parallel
         if active_module is not None:
@@ -180,11 +266,16 @@ def adapt_step(P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Op
     if geo:
         data["depths"] = depths
         render_kwargs = dict(render_kwargs, depth_eps=depth_eps, **geo)
+    if appearance is not None:
+        data["img_indices"] = img_indices
+        render_kwargs = dict(render_kwargs, appearance=appearance, appearance_reg=appearance_reg)
     loss = compute_loss(P, model=base, data=data, params=None, active_module=active_module,
                         reduction="mean", distortion_weight=distortion_weight, proposal=proposal,
                         interlevel_weight=interlevel_weight, **render_kwargs)
     # without FusedAdam the clip norm is taken over the base's and the proposal's parameters together
     clipped = base.parameters() if proposal is None else list(base.parameters()) + list(proposal.parameters())
+    if appearance is not None:
+        clipped = list(clipped) + list(appearance.parameters())
     if ops.TRAIN_MLP_PRECISION == "amp":
         scaler = grad_scaler if grad_scaler is not None else torch.amp.GradScaler("cuda")
         scaler.scale(loss).backward()
@@ -219,11 +310,14 @@ class GraphedAdaptStep:
     host synchronisation, so they are captured with the rest.  The proposal-guided step is not captured (use
     adapt_step).  ``depth_weight`` / ``sight_weight`` as in adapt_step: ``depths`` (N,) is copied into a static buffer
     before each replay (pass ``depths=`` per call), ``depth_eps`` is fixed at capture; the depth launch and the count
-    of rays with a target make no host synchronisation."""
+    of rays with a target make no host synchronisation.  ``appearance`` / ``appearance_reg`` as in adapt_step:
+    ``img_indices`` (N,) is kept as a static int32 buffer and copied before each replay (pass ``img_indices=`` per
+    call); the slot gather and the fused loss make no host synchronisation."""
 
     def __init__(self, P, base, rays, rgbs, optimizer, active_module=None, grad_clip: Optional[float] = 1.0,
                  warmup: int = 2, max_steps: int = 1 << 16, distortion_weight: float = 0.0, proposal=None,
-                 depths=None, depth_weight: float = 0.0, sight_weight: float = 0.0, depth_eps=None, **render_kwargs):
+                 depths=None, depth_weight: float = 0.0, sight_weight: float = 0.0, depth_eps=None, img_indices=None,
+                 appearance=None, appearance_reg: float = 0.0, **render_kwargs):
         from .meta_container import MetaContainer
         if proposal is not None:
             raise ValueError("GraphedAdaptStep: the proposal-guided render is not captured; use adapt_step")
@@ -249,6 +343,13 @@ class GraphedAdaptStep:
             if isinstance(depth_eps, torch.Tensor):
                 depth_eps = depth_eps.detach().to(rays.device, torch.float32).clone()
             render_kwargs = dict(render_kwargs, depths=self.static_depths, depth_eps=depth_eps, **geo)
+        self.static_img = None
+        if appearance is not None:
+            if img_indices is None:
+                raise ValueError("GraphedAdaptStep: an appearance model needs img_indices (one image index per ray)")
+            self.static_img = img_indices.detach().to(rays.device, torch.int32).reshape(-1).clone()
+            render_kwargs = dict(render_kwargs, img_indices=self.static_img, appearance=appearance,
+                                 appearance_reg=appearance_reg)
         self.args = (P, base, optimizer, active_module, grad_clip, render_kwargs)
         side = torch.cuda.Stream(rays.device)
         side.wait_stream(torch.cuda.current_stream(rays.device))
@@ -269,7 +370,7 @@ class GraphedAdaptStep:
         self.max_steps = int(max_steps)
 
     def __call__(self, rays: torch.Tensor, rgbs: torch.Tensor, jitter_u: Optional[torch.Tensor] = None,
-                 depths: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 depths: Optional[torch.Tensor] = None, img_indices: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self.replays >= self.max_steps:
             # past the precomputed Adam table the captured update would silently stop
             raise RuntimeError(f"GraphedAdaptStep: {self.max_steps} replays exhausted the Adam constant table; "
@@ -282,6 +383,11 @@ class GraphedAdaptStep:
             if self.static_depths is None:
                 raise ValueError("GraphedAdaptStep: captured without depth supervision; depths cannot be replayed")
             self.static_depths.copy_(depths.reshape(-1), non_blocking=True)
+        if img_indices is not None:
+            if self.static_img is None:
+                raise ValueError("GraphedAdaptStep: captured without an appearance model; img_indices cannot be "
+                                 "replayed")
+            self.static_img.copy_(img_indices.reshape(-1), non_blocking=True)
         self.graph.replay()
         self.replays += 1
         from .optim import bump_versions
@@ -329,7 +435,7 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
                   active_module: Optional[int] = None, grad_clip: Optional[float] = 1.0,
                   distortion_weight: float = 0.0, proposal=None, interlevel_weight: float = 1.0,
                   n_importance: int = 0, depth_weight: float = 0.0, sight_weight: float = 0.0,
-                  depth_eps=None) -> Dict[str, float]:
+                  depth_eps=None, appearance=None, appearance_reg: float = 0.0) -> Dict[str, float]:
     """runtime_adapt.py:213-315: adapt in place; one pass over the loader (steps=None) or exactly
     ``steps`` updates cycling over it.
 
@@ -344,7 +450,10 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
     ``interlevel_weight`` times the interlevel loss; the proposal, whose parameters must be in ``optimizer``, is put in
     training mode too.  ``depth_weight`` / ``sight_weight`` > 0 add depth supervision (adapt_step) and take the eager
     step as well: the loader then yields (rays, rgbs, depths), ``depth_eps`` is the half-width.  With both 0 the loader
-    may yield pairs or triples; the depths are not used."""
+    may yield pairs or triples; the depths are not used.  ``appearance`` (an appearance.AppearanceAffine, some of its
+    parameters in ``optimizer``) trains on the per-image corrected colour, plus ``appearance_reg`` times its
+    regulariser (adapt_step), and takes the eager step as well: the loader then yields
+    (rays, rgbs, depths_or_None, img_indices); the module is put in training mode too."""
     geo = bool(depth_weight or sight_weight)
     if geo and depth_eps is None:
         raise ValueError("runtime_adapt: depth_weight / sight_weight need depth_eps")
@@ -352,6 +461,8 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
     model.train()
     if proposal is not None:
         proposal.train()
+    if appearance is not None:
+        appearance.train()
     # the reference clips base.parameters(); parameters outside base get no gradient from the loss
     # (zero_grad sets them to None), so FusedAdam's norm over gradient-carrying tensors is the same
     base = model.submodules[active_module] if active_module is not None else model
@@ -363,13 +474,15 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
         extra["n_importance"] = int(n_importance)
     if geo:
         extra.update(depth_weight=float(depth_weight), sight_weight=float(sight_weight), depth_eps=depth_eps)
+    if appearance is not None:
+        extra.update(appearance=appearance, appearance_reg=float(appearance_reg))
     fast = [None, active_module is None and not distortion_weight and not extra]   # [RoutedAdaptStep, worth trying]
     # use_amp: a fresh GradScaler per call (runtime_adapt.py:237); the cached RoutedAdaptStep's scaler restarts too
     amp = ops.TRAIN_MLP_PRECISION == "amp"
     scaler = torch.amp.GradScaler("cuda") if amp else None
     reset = set()
 
-    def run(rays, rgbs, depths=None):
+    def run(rays, rgbs, depths=None, img_indices=None):
         nonlocal last_loss, step_count
         rays, rgbs = rays.to(device, non_blocking=True), rgbs.to(device, non_blocking=True)
         more = {}
@@ -377,6 +490,11 @@ def runtime_adapt(*, P, model, data_loader: Iterable, optimizer, steps: Optional
             if depths is None:
                 raise ValueError("runtime_adapt: depth_weight / sight_weight need loader items (rays, rgbs, depths)")
             more["depths"] = depths.to(device, non_blocking=True)
+        if appearance is not None:
+            if img_indices is None:
+                raise ValueError("runtime_adapt: an appearance model needs loader items (rays, rgbs, depths_or_None, "
+                                 "img_indices)")
+            more["img_indices"] = img_indices.to(device, non_blocking=True)
         if fast[1] and (fast[0] is None or rays.shape[0] > fast[0].N):
             fast[0] = _routed_step_for(P, base, optimizer, int(rays.shape[0]), grad_clip)
             fast[1] = fast[0] is not None

@@ -935,6 +935,29 @@ int acn_mse_linear_fwd_ws(const float* pred, const float* gt, int64_t n, float* 
 int acn_mse_linear_bwd(const float* pred, const float* gt, int64_t n, const float* g_loss, float* g_pred,
                        void* stream);
 
+/* ---- per-image exposure correction: the affine colour transform c = A[s] p + b[s] of a ray's image
+ * slot s on the composited pixel p, fused with the loss above and all of its gradients, in one launch.
+ * pred, gt (N, 3); slot (N) int32; A (I, 3, 3) row major, b (I, 3).  Per ray r, slot s, channel k, n = 3 N:
+ *   c      = fl32(A[s,k,0] p0 + A[s,k,1] p1 + A[s,k,2] p2 + b[s,k])  in double, left to right, rounded once;
+ *            a slot < 0 or >= I is the identity: c = p_k bit for bit, and no parameter gradient
+ *   d      = clamp01(c) - gt_linear(gt)  in fp32, as acn_mse_linear_fwd (NaN passes the clamps)
+ *   loss   = fl32(sum d^2 / n), double, fixed order
+ *   g_c    = fl32((2 / n) d) where 0 <= c <= 1, else 0   (acn_mse_linear_bwd at g_loss = 1)
+ *   g_pred[r,j] = fl32(sum_k A[s,k,j] g_c[k])   (g_c[j] for the identity)
+ *   g_A[i,k,j]  = fl32(sum_{r: slot = i} g_c[r,k] p[r,j]),  g_b[i,k] = fl32(sum_{r: slot = i} g_c[r,k])
+ * Sums and products in double, every output rounded once and every output element written (a slot no ray reached
+ * gets zeros; no pre-zeroing).  g_pred, g_A, g_b may be NULL together: the gradient work is skipped, the loss has the
+ * same bits.  Bitwise reproducible (no atomics on the outputs), no host synchronisation, capturable.
+ * workspace: acn_appearance_mse_workspace_bytes(I) bytes, ZEROED once before first use (the call leaves its counter
+ * at 0 again); one workspace per stream. */
+size_t acn_appearance_mse_workspace_bytes(int I);
+int acn_appearance_mse(const float* pred, const float* gt, const int32_t* slot, int64_t N, const float* A,
+                       const float* b, int I, float* loss, float* g_pred, float* g_A, float* g_b, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* The correction alone, elementwise: out[r,k] = c as above (not clamped); slot outside [0, I) copies the input. */
+int acn_appearance_apply(const float* rgb, const int32_t* slot, int64_t N, const float* A, const float* b, int I,
+                         float* out, void* stream);
+
 
 /* The training MLP in exact fp32 (v_mfma_f32_32x32x2_f32 layer products instead of the fp32-accurate fp16x3
  * split): the same twelve entry points, suffixed _exact, same arguments and semantics; workspaces must come

@@ -6,13 +6,14 @@ Reads hipcc's -Rpass-analysis=kernel-resource-usage remarks of every object and 
 has a non-zero 'VGPRs Spill' or 'ScratchSize': a spilled register in these kernels is a scratch round trip per
 use on the hot path, and the round-5 self-check builds put spilled 64-bit addresses next to wrong results.
 Hot kernels (demangled-name substrings): the C2 / C3-C4 renders, the one-expert-per-GPU owner kernel, the meta
-MLP backward, the hash grid's and the MLP's input gradients, the distortion loss, the depth loss, the importance resampling, the SSIM forward and gradient, the interlevel loss.  --all lists every kernel with its VGPRs, spills and scratch.
+MLP backward, the hash grid's and the MLP's input gradients, the distortion loss, the depth loss, the importance resampling, the SSIM forward and gradient, the interlevel loss, the appearance loss.  --all lists every kernel with its VGPRs, spills and scratch.
 """
 import argparse, re, sys
 
 HOT = ("render_ws_kernel", "render_slots_kernel", "render_wss_kernel", "ep_field_kernel", "mlp_bwd_dw_pc_kernel",
        "mlp_bwd_dw_pairs_pc_kernel", "hashgrid_bwd_input", "mlp_bwd_input", "field_sigma_grad", "distortion_kernel",
-       "resample_pdf_kernel", "ssim_fwd_kernel", "ssim_grad_kernel", "interlevel_loss_kernel", "depth_loss_kernel")
+       "resample_pdf_kernel", "ssim_fwd_kernel", "ssim_grad_kernel", "interlevel_loss_kernel", "depth_loss_kernel",
+       "appearance_mse_kernel")
 FIELDS = {"VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "VGPRs Spill": "vspill",
           "SGPRs Spill": "sspill", "Occupancy [waves/SIMD]": "occ"}
 
